@@ -24,7 +24,7 @@ bound and split exactly into two fp16 planes (22 significant bits), three MFMAs 
 with fp32 accumulation. Measured closer to fp64 than PyTorch's fp32 GEMMs on every
 ResNet-50 shape (tests/test_fp32_path.py). ``MPIT_F32_SPLIT=bf16x6`` selects the 6-MFMA bf16
 split instead. bf16 autocast (fp32 master weights) is reported as the secondary field
-``secondary.bf16_autocast`` of the same job.
+``secondary.bf16_autocast`` of the same job (``--full``).
 
 The last pulls of a step are waited for at the end of that step (the reference's
 push, pull, wait: asyncsgd/optim-downpour.lua:50-53); ``--defer-ps-wait`` retires them at
@@ -34,7 +34,16 @@ the next step's first read of the weights instead (measured slower, off by defau
 The next step's weight casts are queued as soon as a step's pulls have landed (the weights
 change only by the pulls; mpit_amd/train.py precast): that is part of each timed step.
 
-Also reported, outside the timed region (``--no-secondary`` skips them):
+A plain run sets up, warms up, times ``--steps`` steps, writes ``--dump-outputs`` and prints
+the result line; nothing else (at N > 1 the pre-flight check that picks the data plane is
+part of the set-up). ``--dump-outputs DIR`` writes what the last timed step handed its caller
+as ``DIR/<name>.npy`` (float32): ``loss`` (the step's return value) and ``params`` (the flat
+weights the step updated in place; the same seeded sample of them in every run when they
+exceed 32 MiB). Model, batch and labels are seeded, so two runs with the same arguments
+start from identical inputs.
+
+``--full`` adds, outside the timed region (``--no-secondary`` then skips the timed ones):
+* ``secondary.bf16_autocast``: the other precision on the same replicas;
 * ``ps_check``: after the run every worker pulls every shard again and the exact bit-sums
   of each shard must agree between all workers and the owning server (exit status 3 if
   not); ``world`` / ``rccl``: the ranks and the collective backend actually seen;
@@ -132,6 +141,25 @@ def _rccl_probe(W, tr, st) -> dict:
     return out
 
 
+_DUMP_FULL_BYTES = 32 << 20  # larger arrays are written as a seeded sample of this many bytes
+
+
+def _dump_outputs(directory: str, tr, loss) -> None:
+    """What the last timed step handed its caller, as float32 ``<name>.npy`` files: the loss it
+    returned and the flat parameters it updated in place (all pulls waited for)."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    tr.sync()
+    if loss is not None:
+        np.save(os.path.join(directory, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    w = tr.flat.flat.detach().float().reshape(-1).cpu().numpy()
+    if w.nbytes > _DUMP_FULL_BYTES:
+        idx = np.sort(np.random.default_rng(20240607).choice(w.size, _DUMP_FULL_BYTES // 4, replace=False))
+        w = w[idx]
+    np.save(os.path.join(directory, "params.npy"), np.ascontiguousarray(w, dtype=np.float32))
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -155,7 +183,15 @@ def main(argv=None) -> int:
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"],
                     help="headline compute precision (fp32 = the reference's; bf16 = autocast, fp32 master)")
     ap.add_argument("--no-amp", action="store_true", help="alias of --dtype fp32 (kept for old scripts)")
-    ap.add_argument("--no-secondary", action="store_true", help="headline only")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run what takes runs or checks of its own: the other "
+                         "precision, the post-run PS check, at N > 1 the RCCL probe, the dedicated topology, "
+                         "the PS ping-pong and the Allreduce time")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="with --full: skip the timed secondary runs (the checks still run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned (loss, updated flat "
+                         "parameters) as DIR/<name>.npy, float32")
     ap.add_argument("--no-channels-last", action="store_true")
     ap.add_argument("--emulate-shards", type=int, default=1,
                     help="K > 1: split the (single) server's shard into K shards, each pushed from inside the "
@@ -233,6 +269,8 @@ def main(argv=None) -> int:
         if fallback is not None:
             preflight["fallback"] = fallback
     secs, loss = mp_train.timed_steps(tr, a.steps, a.warmup)
+    if a.dump_outputs and tr.is_worker and W.Get_rank() == tr.cranks[0]:
+        _dump_outputs(a.dump_outputs, tr, loss)
     peak_gib = round(torch.cuda.max_memory_allocated(tr.device) / 2 ** 30, 2) if tr.on_gpu else None
     nworkers = len(tr.cranks)
     shape = INPUT_SHAPES.get(a.model, (3, 224, 224))
@@ -244,7 +282,7 @@ def main(argv=None) -> int:
     secondary = {}
     t_sec = time.perf_counter()
     sec_steps, sec_warm = max(3, min(a.steps, 20)), max(4, a.warmup)
-    if not a.no_secondary and tr.on_gpu:
+    if a.full and not a.no_secondary and tr.on_gpu:
         # the other precision on the same replicas / PS (bf16 autocast when the headline is fp32)
         tr.set_amp(not amp)
         s2, _ = mp_train.timed_steps(tr, sec_steps, sec_warm)
@@ -253,12 +291,12 @@ def main(argv=None) -> int:
             "ms_per_step": round(1000.0 * s2 / sec_steps, 3), "steps": sec_steps, "warmup": sec_warm,
             "dtype": "bf16" if not amp else "fp32", "parallelism": par}
         tr.set_amp(amp)
-    check = tr.verify_ps() if (tr.pc is not None or tr.ps_server is not None) else None
+    check = tr.verify_ps() if a.full and (tr.pc is not None or tr.ps_server is not None) else None
     tr.stop()
     st = mp.runtime.state()
     devices = _devices(W, tr)
-    rccl = _rccl_probe(W, tr, st) if world > 1 else None
-    if not a.no_secondary and world > 1 and a.optimizer != "allreduce":
+    rccl = _rccl_probe(W, tr, st) if a.full and world > 1 else None
+    if a.full and not a.no_secondary and world > 1 and a.optimizer != "allreduce":
         from mpit_amd.instruments import allreduce_time, ps_pingpong
 
         try:
@@ -302,6 +340,7 @@ def main(argv=None) -> int:
             "world": st.world, "shared_devices": st.shared_devices, "devices": devices, "rccl": rccl,
             "ps_check": check, "preflight": preflight, "peak_mem_gib": peak_gib,
             **({"emulate_shards": a.emulate_shards} if a.emulate_shards > 1 else {}),
+            "full": a.full,
             "secondary": secondary,
             "secondary_s": round(time.perf_counter() - t_sec, 2),
         }

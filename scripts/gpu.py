@@ -12,7 +12,7 @@ Steps:
   tier                  pytest -m gpu (whole GPU tier)                  -> pytest_gpu.log
   pytest:<args>[:K=V;K=V] pytest <args> (e.g. pytest:tests/test_overlap.py), extra env -> pytest_<n>.log
   pytestall:<args>[:K=V] the same without -x (a diagnosis run: every test reports)
-  bench                 bench.py defaults (fp32 headline + bf16 secondary) -> bench.json
+  bench                 bench.py --full (fp32 headline + bf16 secondary, PS check) -> bench_<n>.json
   bench:<args>[:K=V;K=V] bench.py <args> (comma separated), extra env    -> bench_<n>.json
   dbench:<n>:<args>     bench.py on n ranks sharing the box's GPU (rehearsal) -> dbench_<n>.json
   prof:<name>:<args>[:K=V;K=V] rocprofv3 --kernel-trace of bench.py <args> (extra env) + stream table -> streams_<name>.md
@@ -92,7 +92,7 @@ def main(argv) -> int:
             print(_tail(os.path.join(out, f"pytest_{i}.log"), 2))
         elif kind == "bench":
             parts = rest.split(":")
-            args = parts[0].split(",") if parts[0] else []
+            args = parts[0].split(",") if parts[0] else ["--full"]
             env = dict(kv.split("=", 1) for kv in parts[1].split(";")) if len(parts) > 1 and parts[1] else {}
             rc = _run(out, f"bench_{i}.err", [PY, "-u", "bench.py"] + args, 600, stdout_file=f"bench_{i}.json", env=env)
             print(_tail(os.path.join(out, f"bench_{i}.json"), 1)[:600])

@@ -80,6 +80,9 @@ except RuntimeError as e:
     # a deadlocked FIFO: report and leave without the stop protocol (it cannot complete)
     print(f"RANK {rank} RESULT RDV_TIMEOUT after {time.time() - t0:.1f}s", flush=True)
     sys.stdout.flush()
+    # leave as a clean exit: a rank whose own wait runs out later must not take this one's
+    # disappearance for a crash (the failure detector would end it with status 70)
+    mp.runtime.state().engine.shutdown()
     os._exit(0)
 stats = srv.stats() if srv is not None else None
 if pc is not None:

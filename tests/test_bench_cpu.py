@@ -14,7 +14,7 @@ def test_bench_three_ranks_cpu():
     e["PYTHONPATH"] = ROOT + os.pathsep + e.get("PYTHONPATH", "")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=3",
            "--master-addr=127.0.0.1", f"--master-port={free_port()}", os.path.join(ROOT, "bench.py"), "--gpus", "3",
-           "--model", "cnn7", "--batch", "8", "--steps", "2", "--warmup", "1"]
+           "--model", "cnn7", "--batch", "8", "--steps", "2", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400, env=e, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -39,7 +39,7 @@ def test_bench_preflight_falls_back_to_datapath3_cpu():
     e["PYTHONPATH"] = ROOT + os.pathsep + e.get("PYTHONPATH", "")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=3",
            "--master-addr=127.0.0.1", f"--master-port={free_port()}", os.path.join(ROOT, "bench.py"), "--gpus", "3",
-           "--model", "cnn7", "--batch", "8", "--steps", "2", "--warmup", "1", "--no-secondary"]
+           "--model", "cnn7", "--batch", "8", "--steps", "2", "--warmup", "1", "--full", "--no-secondary"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400, env=e, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -56,7 +56,7 @@ def test_bench_no_peer_access_falls_back_to_datapath3_cpu():
     e["PYTHONPATH"] = ROOT + os.pathsep + e.get("PYTHONPATH", "")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=3",
            "--master-addr=127.0.0.1", f"--master-port={free_port()}", os.path.join(ROOT, "bench.py"), "--gpus", "3",
-           "--model", "cnn7", "--batch", "8", "--steps", "2", "--warmup", "1", "--no-secondary"]
+           "--model", "cnn7", "--batch", "8", "--steps", "2", "--warmup", "1", "--full", "--no-secondary"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400, env=e, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])

@@ -7,12 +7,10 @@ import pytest
 
 from mpit_amd.utils import t7
 
-REF = "/root/reference/BiCNN"
-needs_ref = pytest.mark.skipif(not os.path.exists(os.path.join(REF, "binary_mapWordStr2WordIdx")),
-                               reason="reference checkout with the BiCNN vocabulary caches not present")
+# the two vocabulary caches as the reference ships them (data files, 607 KiB each)
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bicnn")
 
 
-@needs_ref
 def test_shipped_vocabulary_maps_are_inverse():
     s2i = t7.load(os.path.join(REF, "binary_mapWordStr2WordIdx"))
     i2s = t7.load(os.path.join(REF, "binary_mapWordIdx2WordStr"))
@@ -23,7 +21,6 @@ def test_shipped_vocabulary_maps_are_inverse():
     assert s2i["SENTBEGIN"] == 1 and s2i["SENTEND"] == 2 and i2s[1] == "SENTBEGIN" and i2s[2] == "SENTEND"
 
 
-@needs_ref
 def test_bicnn_preload_binary_builds_vocabulary_from_t7_maps():
     from mpit_amd.apps import bicnn
     from mpit_amd.apps.qa_data import load_t7_vocab
@@ -65,7 +62,6 @@ def test_t7_rejects_truncated_and_trailing():
         t7.loads(blob + b"\0")
 
 
-@needs_ref
 def test_bicnn_preload_binary_prefers_the_binary_file(tmp_path, capsys):
     """-preloadBinary takes --binaryFile when it exists, even next to the Torch7 maps; the
     vocabulary-only mode says loudly that its questions / answers are synthetic."""
