@@ -486,7 +486,24 @@ PYBIND11_MODULE(_mpit, m) {
       .def("lock", &Window::lock, py::call_guard<py::gil_scoped_release>())
       .def("try_lock", &Window::try_lock)
       .def("unlock", &Window::unlock)
-      .def("flush", [](Window& w, uintptr_t s) { w.flush(S(s)); }, py::call_guard<py::gil_scoped_release>());
+      .def("flush", [](Window& w, uintptr_t s) { w.flush(S(s)); }, py::call_guard<py::gil_scoped_release>())
+      .def("sync", &Window::sync, py::call_guard<py::gil_scoped_release>())
+      .def_property_readonly("allreduce_capable", &Window::allreduce_capable)
+      .def("allreduce",
+           [](Window& w, int64_t off, int64_t nelem, int dtype, int op, uintptr_t s, int mode, uintptr_t dst) {
+             return w.allreduce(off, nelem, dtype, op, S(s), mode, dst);
+           },
+           py::arg("off"), py::arg("nelem"), py::arg("dtype"), py::arg("op"), py::arg("stream"), py::arg("mode") = 0,
+           py::arg("dst") = 0, py::call_guard<py::gil_scoped_release>());
+  m.def("peer_reduce_supported", &peer_reduce_supported, py::arg("op"), py::arg("dtype"));
+  m.def(
+      "peer_reduce",
+      [](int dev, uintptr_t s, int op, int dtype, std::vector<uintptr_t> srcs, std::vector<uintptr_t> dsts, int64_t n) {
+        peer_reduce(dev, S(s), op, dtype, srcs, dsts, n);
+      },
+      py::arg("dev"), py::arg("stream"), py::arg("op"), py::arg("dtype"), py::arg("srcs"), py::arg("dsts"),
+      py::arg("n"), py::call_guard<py::gil_scoped_release>());
+  m.def("ar_oneshot_bytes", &Window::oneshot_bytes);
 
   py::class_<ServerRule>(m, "ServerRule")
       .def(py::init<>())

@@ -163,6 +163,8 @@ class Engine {
   }
   // deadlines (seconds, 0 = none): MPIT_WAIT_TIMEOUT_S for Wait/Probe/Barrier
   static double wait_timeout_s();
+  // the abort check of every wait loop, for waits outside the engine (Window::sync)
+  void poll_abort() { check_abort(); }
 
   hipStream_t comm_stream() const { return stream_; }
   // IPC helpers (also used by windows)

@@ -6,7 +6,9 @@
 #include <unistd.h>
 #include <xmmintrin.h>
 
+#include <algorithm>
 #include <chrono>
+#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <stdexcept>
@@ -26,6 +28,7 @@ struct Blob {
   int64_t bytes;
   int32_t device;
   int32_t world_rank;
+  int32_t align;  // base address mod 16 in the owner's address space
   int64_t offset;
   hipIpcMemHandle_t handle;
   char ctl_name[160];
@@ -84,6 +87,14 @@ Window::~Window() {
     if (r.map && r.map != ctl_map_) ::munmap(r.map, std::max<int64_t>(r.map_bytes, 64));
   if (ctl_map_) ::munmap(ctl_map_, std::max<int64_t>(ctl_map_bytes_, 64));
   ::shm_unlink(ctl_name_.c_str());
+  if (ar_tmp_) {
+    if (device_) {
+      hipSetDevice(eng_.device());
+      hipFree(ar_tmp_);
+    } else {
+      std::free(ar_tmp_);
+    }
+  }
   if (own_ && local_) {
     hipSetDevice(eng_.device());
     hipFree(local_);
@@ -95,6 +106,7 @@ std::string Window::blob() const {
   b.bytes = bytes_;
   b.device = device_ ? 1 : 0;
   b.world_rank = eng_.rank();
+  b.align = int32_t(reinterpret_cast<uintptr_t>(local_) & 15);
   std::strncpy(b.ctl_name, ctl_name_.c_str(), sizeof(b.ctl_name) - 1);
   if (device_ && local_ && bytes_ > 0) {
     hipw(hipSetDevice(eng_.device()), "hipSetDevice");
@@ -114,6 +126,7 @@ void Window::connect(const std::vector<std::string>& blobs, const std::vector<in
     r.bytes = b.bytes;
     r.device = b.device != 0;
     r.world_rank = b.world_rank;
+    r.align = b.align;
     if (world_ranks.size() == blobs.size() && world_ranks[m] != b.world_rank)
       throw std::invalid_argument("mpit: window member order mismatch");
     if (b.world_rank == eng_.rank()) {
@@ -138,6 +151,16 @@ void Window::connect(const std::vector<std::string>& blobs, const std::vector<in
       }
     }
   }
+  check_alignment();
+}
+
+// Window::allreduce cuts its slices at 16-byte addresses computed from the
+// owners' published alignment; a mapping that does not keep it would make ranks disagree.
+void Window::check_alignment() const {
+  for (const Remote& r : remote_)
+    if (r.ptr && int(reinterpret_cast<uintptr_t>(r.ptr) & 15) != r.align)
+      throw std::runtime_error("mpit: window " + std::to_string(id_) + " of rank " + std::to_string(r.world_rank) +
+                               " is mapped at another 16-byte alignment than its owner's");
 }
 
 void Window::unlink_names() { ::shm_unlink(ctl_name_.c_str()); }
@@ -237,6 +260,121 @@ void Window::flush(hipStream_t s) {
     hipw(hipSetDevice(eng_.device()), "hipSetDevice");
     hipw(hipStreamSynchronize(s), "Win_flush");
   }
+}
+
+void Window::sync() {
+  const int64_t mine = ctl_->epoch.fetch_add(1, std::memory_order_release) + 1;
+  const double tmo = Engine::wait_timeout_s();
+  const auto t0 = std::chrono::steady_clock::now();
+  for (const Remote& r : remote_) {
+    if (r.ctl == ctl_) continue;
+    int spins = 0;
+    while (r.ctl->epoch.load(std::memory_order_acquire) < mine) {
+      eng_.poll_abort();
+      if (++spins < 2000) {
+        _mm_pause();
+      } else if (spins < 2256) {
+        std::this_thread::yield();
+      } else {
+        std::this_thread::sleep_for(std::chrono::microseconds(20));
+        if (tmo > 0 && (spins & 255) == 0 &&
+            std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > tmo)
+          eng_.fatal("window " + std::to_string(id_) + " sync timed out after " + std::to_string(int(tmo)) +
+                     " s waiting for rank " + std::to_string(r.world_rank) + " (MPIT_WAIT_TIMEOUT_S)");
+      }
+    }
+  }
+}
+
+int64_t Window::oneshot_bytes() {
+  // Default 0: two-shot at every size. With the ranks sharing one GPU (all this pool can
+  // measure, profiles/win_allreduce.md) one-shot never wins: it reads n times the bytes and
+  // pays a copy-back after the second barrier. Across distinct GPUs a small message may
+  // prefer it (one hop less); set the crossover measured there.
+  const char* e = std::getenv("MPIT_AR_ONESHOT_BYTES");
+  return e && *e ? std::atoll(e) : 0;
+}
+
+bool Window::allreduce_capable() const {
+  if (remote_.empty() || remote_.size() > size_t(kPeerMax)) return false;
+  for (const Remote& r : remote_)
+    if (r.device != device_ || (r.bytes > 0 && !r.ptr)) return false;
+  return true;
+}
+
+bool Window::allreduce(int64_t off, int64_t nelem, int dtype, int op, hipStream_t s, int mode, uintptr_t dst) {
+  if (!allreduce_capable() || !peer_reduce_supported(op, dtype)) return false;
+  const int64_t es = peer_dtype_size(dtype);
+  const int n = int(remote_.size());
+  if (off < 0 || nelem < 0 || off % es) throw std::invalid_argument("mpit: window all-reduce range misaligned");
+  for (const Remote& r : remote_)
+    if (off + nelem * es > r.bytes) throw std::out_of_range("mpit: all-reduce range outside a member's window");
+  const int dev = device_ ? eng_.device() : -1;
+  auto drain = [&](const char* what) {
+    if (dev >= 0) hipw(hipStreamSynchronize(s), what);
+  };
+  if (dev >= 0) hipw(hipSetDevice(dev), "hipSetDevice");
+  int me = -1;
+  std::vector<uintptr_t> ptrs(static_cast<size_t>(n));
+  for (int m = 0; m < n; ++m) {
+    ptrs[size_t(m)] = reinterpret_cast<uintptr_t>(remote_[size_t(m)].ptr) + uintptr_t(off);
+    if (remote_[size_t(m)].ctl == ctl_) me = m;
+  }
+  if (me < 0) throw std::runtime_error("mpit: window all-reduce on a rank that is no member");
+  const bool oneshot = dst != 0 || mode == kArOneShot || (mode == kArAuto && nelem * es <= oneshot_bytes());
+  drain("all-reduce B1");
+  sync();  // B1: every member's input is complete
+  if (nelem > 0 && !oneshot) {
+    // two-shot push: rank r reduces slice r from all members and stores it into all members.
+    // Interior bounds rounded down to a 16-B address of member 0's range, from the alignment
+    // member 0 published in its blob (checked against every mapping at connect), so every
+    // rank computes the same bounds.
+    auto bound = [&](int k) -> int64_t {
+      if (k <= 0) return 0;
+      if (k >= n) return nelem;
+      const int64_t b = nelem * k / n;
+      const int64_t a = ((int64_t(remote_[0].align) + off + b * es) & 15) / es;
+      return std::max<int64_t>(0, b - a);
+    };
+    const int64_t lo = bound(me), hi = bound(me + 1);
+    if (hi > lo) {
+      std::vector<uintptr_t> sl(ptrs);
+      for (auto& p : sl) p += uintptr_t(lo * es);
+      peer_reduce(dev, s, op, dtype, sl, sl, hi - lo);
+    }
+  } else if (nelem > 0) {
+    // one-shot: every rank reduces the whole range. My window must stay as it is until B2 (a
+    // slower peer may still be reading it): the result goes to `dst`, or to a private buffer
+    // copied back after B2.
+    uintptr_t out = dst;
+    if (!out) {
+      if (ar_tmp_bytes_ < nelem * es) {
+        if (ar_tmp_) {
+          if (dev >= 0) hipw(hipFree(ar_tmp_), "hipFree(all-reduce tmp)");
+          else std::free(ar_tmp_);
+          ar_tmp_ = nullptr;
+        }
+        const int64_t cap = std::max<int64_t>(nelem * es, 64 << 10);
+        if (dev >= 0) hipw(hipMalloc(&ar_tmp_, size_t(cap)), "hipMalloc(all-reduce tmp)");
+        else if (!(ar_tmp_ = std::malloc(size_t(cap)))) throw std::bad_alloc();
+        ar_tmp_bytes_ = cap;
+      }
+      out = reinterpret_cast<uintptr_t>(ar_tmp_);
+    }
+    peer_reduce(dev, s, op, dtype, ptrs, {out}, nelem);
+  }
+  drain("all-reduce B2");
+  sync();  // B2: every slice has landed everywhere and every read of my memory is finished
+  if (nelem > 0 && oneshot && !dst) {
+    void* mine = reinterpret_cast<void*>(ptrs[size_t(me)]);
+    if (dev >= 0) {
+      hipw(hipMemcpyAsync(mine, ar_tmp_, size_t(nelem * es), hipMemcpyDeviceToDevice, s), "all-reduce copy back");
+      drain("all-reduce copy back");
+    } else {
+      std::memcpy(mine, ar_tmp_, size_t(nelem * es));
+    }
+  }
+  return true;
 }
 
 }  // namespace mpit

@@ -43,6 +43,7 @@ class Window {
   // shard data as messages and never touches a peer allocation)
   void connect(const std::vector<std::string>& blobs, const std::vector<int>& world_ranks, bool map_remote = true);
   void unlink_names();  // after every member connected
+  void check_alignment() const;
 
   uintptr_t local_ptr() const { return reinterpret_cast<uintptr_t>(local_); }
   int64_t bytes() const { return bytes_; }
@@ -64,6 +65,22 @@ class Window {
   void unlock(int m);
   void flush(hipStream_t s);  // complete all operations this rank issued on stream s
 
+  // Barrier among this window's members only, on the per-rank epoch counters of the control
+  // blocks (monotonic: bump mine with release, wait with acquire until every member's reached
+  // it). Independent of Engine::barrier(), whose single world-wide counter pair another thread
+  // of this rank may be inside at the same time. One thread per window at a time.
+  void sync();
+  // In-place all-reduce of nelem elements at byte offset `off` of every member's window
+  // (kernels.h peer_reduce; member order = fold order, so the result is bitwise identical on
+  // every rank). Blocking. mode: 0 = by size (MPIT_AR_ONESHOT_BYTES), 1 = one-shot, 2 = two-shot.
+  // dst != 0: one-shot into that local buffer instead of the window (the window keeps the input).
+  // Returns false, before any synchronisation, when this window cannot run it (more than 8
+  // members, a member not mapped, mixed host / device members): the caller falls back.
+  enum ArMode : int { kArAuto = 0, kArOneShot = 1, kArTwoShot = 2 };
+  bool allreduce(int64_t off, int64_t nelem, int dtype, int op, hipStream_t s, int mode = kArAuto, uintptr_t dst = 0);
+  bool allreduce_capable() const;
+  static int64_t oneshot_bytes();  // MPIT_AR_ONESHOT_BYTES
+
  private:
   Engine& eng_;
   int64_t id_;
@@ -80,12 +97,15 @@ class Window {
     int64_t bytes = 0;
     bool device = false;
     int world_rank = -1;
+    int align = 0;  // the owner's base address mod 16, from its blob (the same on every rank)
     WinCtl* ctl = nullptr;
     void* map = nullptr;
     int64_t map_bytes = 0;
   };
   std::vector<Remote> remote_;
   std::vector<int> held_;  // lock mode held per member: 0 none, 1 shared, 2 exclusive
+  void* ar_tmp_ = nullptr;  // one-shot in place: the private result, copied back after B2
+  int64_t ar_tmp_bytes_ = 0;
 };
 
 }  // namespace mpit

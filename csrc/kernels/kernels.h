@@ -292,4 +292,19 @@ int64_t maxpool_bwd_ws_floats(int C);
 // global average pool backward over NHWC: dx[n][p][c] = dy[n][c] / HW (bf16 / fp32)
 void avgpool_bwd(int dev, hipStream_t s, int N, int HW, int C, uintptr_t dy, uintptr_t dx, bool f32 = false);
 
+// ---- peer reduce: the reducer of the window all-reduce (allreduce.hip) ---------------
+enum PeerOp : int { kPrSum = 0, kPrProd, kPrMax, kPrMin, kPrLand, kPrLor, kPrLxor, kPrBand, kPrBor, kPrBxor, kPrOps };
+enum PeerDtype : int { kPrF32 = 0, kPrBf16, kPrF16, kPrF64, kPrI32, kPrI64, kPrU8, kPrDtypes };
+constexpr int kPeerMax = 8;
+// dst[j][i] = src[0][i] (op) src[1][i] (op) ... (op) src[ns-1][i], i < n, for every j < nd:
+// a left fold in the order given; 1 <= ns <= 8, 1 <= nd <= 8; dev < 0 -> host twin.
+// bf16 / fp16 SUM and PROD accumulate in fp32 and round to nearest-even once at the store;
+// MAX / MIN propagate NaN; LAND / LOR / LXOR: non-zero is true, result 0 or 1 in the dtype;
+// BAND / BOR / BXOR: integer dtypes only. dst[j] may be src[j] (in place); nothing else may
+// alias. The kernel holds no cross-rank synchronisation: visibility rests on its boundaries.
+bool peer_reduce_supported(int op, int dtype);
+int peer_dtype_size(int dtype);
+void peer_reduce(int dev, hipStream_t s, int op, int dtype, const std::vector<uintptr_t>& srcs,
+                 const std::vector<uintptr_t>& dsts, int64_t n);
+
 }  // namespace mpit

@@ -10,7 +10,10 @@ Transport is chosen by the tensor's device inside one native core (SURVEY §7.4 
   rendezvous in which the receiver pulls the sender's buffer through HIP IPC (xGMI);
 * collectives on HBM tensors go to RCCL through ``torch.distributed`` whenever every
   member owns a distinct GPU; otherwise (host tensors, or several ranks rehearsing on one
-  GPU) they run as tree / ring algorithms over the point-to-point layer above.
+  GPU) they run as tree / ring algorithms over the point-to-point layer above;
+* opt-in (``algo="window"`` / ``MPIT_ALLREDUCE=window``): all-reduce by the peer-reduce kernel
+  over symmetric memory every member maps (``Comm.sym_alloc`` / ``sym_register``), a left fold
+  in rank order that is bitwise identical on every rank.
 """
 from __future__ import annotations
 
@@ -33,7 +36,11 @@ SUCCESS = 0
 ERR_TRUNCATE = 15
 
 _COLL_OFFSET = 1 << 20  # collective traffic of a communicator uses ctx + this
-_coll_lock = threading.Lock()
+# Background collectives (Comm._bg) run one at a time, in the order they were called: a ticket
+# is drawn on the caller's thread and the background threads are served by ticket. (A plain
+# lock lets the waiting threads in in any order, so two ranks could pair up different calls.)
+_coll_cv = threading.Condition()
+_coll_tickets = [0, 0]  # next ticket to hand out, ticket being served
 
 
 # ============================================================================ Status / Request
@@ -91,7 +98,7 @@ class Request:
     """A non-blocking operation. Keeps its buffers alive until completion."""
 
     def __init__(self, comm=None, rid: Optional[int] = None, keep=(), itemsize=1, on_done: Optional[Callable] = None,
-                 work=None, thread=None, result=None):
+                 work=None, thread=None, result=None, event=None):
         self.comm = comm
         self._rid = rid
         self._keep = keep
@@ -99,10 +106,17 @@ class Request:
         self._on_done = on_done
         self._work = work  # torch.distributed Work
         self._thread = thread  # background collective
+        self._ev = event  # threading.Event set by the communicator's all-reduce worker
         self._status: Optional[Status] = None
         self._result = result
         self._err = None
+        self._inner = None  # the request a persistent Start() took its state from
         self.persistent = None  # (callable) for *_init requests
+
+    def _raise_err(self):
+        err = self._err if self._err is not None else getattr(self._inner, "_err", None)
+        if err is not None:
+            raise err
 
     # -- completion
     def _complete(self, st: Status):
@@ -134,8 +148,13 @@ class Request:
                 return False
             self._thread.join()
             self._thread = None
-            if self._err is not None:
-                raise self._err
+            self._raise_err()
+            self._complete(Status(0, 0, 0, 0))
+        elif self._ev is not None:
+            if not self._ev.is_set():
+                return False
+            self._ev = None
+            self._raise_err()
             self._complete(Status(0, 0, 0, 0))
         else:
             self._complete(Status())
@@ -156,8 +175,12 @@ class Request:
             elif self._thread is not None:
                 self._thread.join()
                 self._thread = None
-                if self._err is not None:
-                    raise self._err
+                self._raise_err()
+                self._complete(Status(0, 0, 0, 0))
+            elif self._ev is not None:
+                self._ev.wait()
+                self._ev = None
+                self._raise_err()
                 self._complete(Status(0, 0, 0, 0))
             else:
                 self._complete(Status())
@@ -200,7 +223,8 @@ class Request:
             raise RuntimeError("Start on a non-persistent request")
         r = self.persistent()
         self._rid, self._keep, self._status = r._rid, r._keep, None
-        self._work, self._thread, self._on_done = r._work, r._thread, r._on_done
+        self._work, self._thread, self._on_done, self._ev = r._work, r._thread, r._on_done, r._ev
+        self._err, self._inner = None, r  # (a background worker reports its error on `r`)
         r._rid = None
         return self
 
@@ -367,6 +391,21 @@ def Reduce_local(inbuf: torch.Tensor, inoutbuf: torch.Tensor, op: Op = SUM):
     return inoutbuf
 
 
+# (op, dtype) codes of the peer-reduce kernel (csrc/kernels/kernels.h PeerOp / PeerDtype)
+_PR_OP_CODE = {SUM: 0, PROD: 1, MAX: 2, MIN: 3, LAND: 4, LOR: 5, LXOR: 6, BAND: 7, BOR: 8, BXOR: 9}
+_PR_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2, torch.float64: 3, torch.int32: 4,
+              torch.int64: 5, torch.uint8: 6}
+
+
+class _SymRec:
+    """A registered symmetric range: [lo, hi) byte addresses of ``tensor``, exposed by ``win``."""
+
+    __slots__ = ("lo", "hi", "win", "tensor", "owned")
+
+    def __init__(self, lo, hi, win, tensor, owned):
+        self.lo, self.hi, self.win, self.tensor, self.owned = lo, hi, win, tensor, owned
+
+
 def _rccl_op(op: Op):
     import torch.distributed as dist
 
@@ -408,6 +447,15 @@ class Comm:
         self._rank = self._ranks.index(me) if me in self._ranks else UNDEFINED
         self._w2c = {w: i for i, w in enumerate(self._ranks)}
         self.topology = None  # set by Cart_create / Graph_create
+        # window all-reduce: registered symmetric memory, staging buffers, the FIFO worker
+        self._sym: list = []  # _SymRec
+        self._ar_stage: dict = {}  # "cuda" | "cpu" -> staging tensor (symmetric, uint8)
+        self._ar_q = None
+        self._ar_thread = None
+        self._ar_stream = None
+        self._ar_lock = threading.Lock()
+        self._ar_calls = {"window": 0, "window_staged": 0, "p2p": 0, "rccl": 0}
+        self._ar_off = False  # a member cannot run Window::allreduce: "window" falls back (agreed)
 
     # ---------------------------------------------------------------- basics
     def Get_rank(self) -> int:
@@ -722,8 +770,12 @@ class Comm:
             _flat(recvbuf).copy_(acc)
         return recvbuf
 
-    def Allreduce(self, sendbuf, recvbuf=None, op: Op = SUM):
-        """MPI_Allreduce (mpifuncs.c:83). ``sendbuf is recvbuf`` (IN_PLACE) allowed."""
+    def Allreduce(self, sendbuf, recvbuf=None, op: Op = SUM, algo: Optional[str] = None):
+        """MPI_Allreduce (mpifuncs.c:83). ``sendbuf is recvbuf`` (IN_PLACE) allowed.
+        ``algo``: None (the MPIT_ALLREDUCE variable, default ``auto``) | ``auto`` (RCCL when
+        every rank owns its GPU, else the point-to-point ring / tree) | ``p2p`` (the ring /
+        tree always) | ``window`` (the peer-reduce kernel over symmetric memory, see
+        :meth:`sym_alloc`; what it cannot run falls back to ``auto``)."""
         if recvbuf is None:
             recvbuf = sendbuf
         n = self.Get_size()
@@ -733,13 +785,21 @@ class Comm:
             if dst.data_ptr() != src.data_ptr():
                 dst.copy_(src)
             return recvbuf
-        if self._use_rccl(src) and _rccl_op(op) is not None:
+        algo = self._ar_algo(algo)
+        if algo == "window" and self._win_ok(src, dst, op):
+            req = self._ar_submit(src, dst, op, keep=(sendbuf, recvbuf))
+            if req is not None:
+                req.Wait()
+                return recvbuf
+        if algo != "p2p" and self._use_rccl(src) and _rccl_op(op) is not None:
             import torch.distributed as dist
 
             if dst.data_ptr() != src.data_ptr():
                 dst.copy_(src)
             dist.all_reduce(dst, op=_rccl_op(op), group=self._pg)
+            self._ar_count("rccl")
             return recvbuf
+        self._ar_count("p2p")
         if op.name in _ELEMENTWISE_OPS and n > 2 and src.numel() >= 64 * n:
             if dst.data_ptr() != src.data_ptr():
                 dst.copy_(src)
@@ -782,12 +842,18 @@ class Comm:
             rq.Wait()
             sq.Wait()
 
-    def Iallreduce(self, sendbuf, recvbuf=None, op: Op = SUM) -> Request:
+    def Iallreduce(self, sendbuf, recvbuf=None, op: Op = SUM, algo: Optional[str] = None) -> Request:
         """Non-blocking all-reduce (mpifuncs.c:1357). RCCL work handle on HBM tensors,
-        a background progress thread otherwise."""
+        a background progress thread otherwise; ``algo="window"``: a ticket in the
+        communicator's all-reduce FIFO (:meth:`Allreduce`, :meth:`_ar_submit`)."""
         if recvbuf is None:
             recvbuf = sendbuf
         src = _flat(sendbuf)
+        algo = self._ar_algo(algo)
+        if self.Get_size() > 1 and algo == "window" and self._win_ok(src, _flat(recvbuf), op):
+            req = self._ar_submit(src, _flat(recvbuf), op, keep=(sendbuf, recvbuf))
+            if req is not None:
+                return req
         if self.Get_size() == 1:
             # one rank: the reduction is the rank's own data — a stream-ordered copy (or
             # nothing, in place), complete at once; no background thread per call
@@ -795,25 +861,233 @@ class Comm:
             if dst.data_ptr() != src.data_ptr():
                 dst.copy_(src)
             return Request(self, keep=(sendbuf, recvbuf))
-        if self._use_rccl(src) and _rccl_op(op) is not None:
+        if algo != "p2p" and self._use_rccl(src) and _rccl_op(op) is not None:
             import torch.distributed as dist
 
             dst = _flat(recvbuf)
             if dst.data_ptr() != src.data_ptr():
                 dst.copy_(src)
             w = dist.all_reduce(dst, op=_rccl_op(op), group=self._pg, async_op=True)
+            self._ar_count("rccl")
             return Request(self, work=w, keep=(sendbuf, recvbuf))
-        return self._bg(lambda: self.Allreduce(sendbuf, recvbuf, op), keep=(sendbuf, recvbuf))
+        fb = "p2p" if algo == "p2p" else "auto"  # (a window request that cannot run is today's routing)
+        return self._bg(lambda: self.Allreduce(sendbuf, recvbuf, op, algo=fb), keep=(sendbuf, recvbuf))
+
+    # ---------------------------------------------------------------- window all-reduce
+    # Symmetric memory + the peer-reduce kernel (csrc/kernels/allreduce.hip) + the two-barrier
+    # protocol of csrc/core/window.cpp Window::allreduce. Every call of this section is
+    # collective over the communicator and must be made in the same order, with the same
+    # registration state of its buffers, on every member.
+    def _ar_algo(self, algo: Optional[str]) -> str:
+        a = (algo if algo is not None else os.environ.get("MPIT_ALLREDUCE", "")) or "auto"
+        if a not in ("auto", "window", "p2p"):
+            raise ValueError(f"all-reduce algo must be auto, window or p2p, not {a!r}")
+        return a
+
+    def _ar_count(self, path: str):
+        with self._ar_lock:
+            self._ar_calls[path] += 1
+
+    def ar_stats(self) -> dict:
+        """All-reduce calls of this communicator per path: ``window`` (of which
+        ``window_staged`` went through the staging buffer), ``p2p``, ``rccl``."""
+        with self._ar_lock:
+            return dict(self._ar_calls)
+
+    def sym_alloc(self, numel: int, dtype=torch.float32, device=None) -> torch.Tensor:
+        """Collective: a tensor of ``numel`` elements backed by a window every member maps (HBM
+        through HIP IPC, or host shm with ``device=False`` / on ranks without a GPU). All-reduces
+        with ``algo="window"`` on it, or on any contiguous view inside it, run in place."""
+        from .window import Win
+
+        if device is None:
+            dev = _rt.device() is not None
+        elif isinstance(device, bool):
+            dev = device
+        else:
+            dev = torch.device(device).type == "cuda"
+        win = Win.Allocate(int(numel), dtype, comm=self, device=dev)
+        return self._sym_add(win, win.tensor, True)
+
+    def sym_register(self, tensor: torch.Tensor) -> torch.Tensor:
+        """Collective: expose an existing HBM tensor zero-copy (``Win.Create``)."""
+        from .window import Win
+
+        if not tensor.is_cuda:
+            raise ValueError("sym_register exposes HBM tensors in place; host memory comes from sym_alloc")
+        return self._sym_add(Win.Create(tensor, self), tensor, False)
+
+    def _sym_add(self, win, t: torch.Tensor, owned: bool) -> torch.Tensor:
+        # Window::allreduce reports "unsupported" per rank (a member it could not map); agree on it
+        # here, collectively, so that every member falls back together instead of one of them
+        # failing while its peers wait in the protocol's barrier
+        if not all(self.allgather_obj(bool(win._w.allreduce_capable))):
+            self._ar_off = True
+        self._sym.append(_SymRec(t.data_ptr(), t.data_ptr() + _nbytes(t), win, t, owned))
+        return t
+
+    def _sym_find(self, t: torch.Tensor):
+        """(record, byte offset) of the registered range that holds all of ``t``, or None."""
+        p, nb = t.data_ptr(), _nbytes(t)
+        for rec in self._sym:
+            if rec.lo <= p and p + nb <= rec.hi and rec.tensor.device == t.device:
+                return rec, p - rec.lo
+        return None
+
+    def sym_free(self, tensor: Optional[torch.Tensor] = None):
+        """Collective: release the symmetric range that holds ``tensor`` (all of them: None)."""
+        if tensor is None:
+            recs = list(self._sym)
+        else:
+            hit = self._sym_find(tensor)
+            if hit is None:
+                raise ValueError("sym_free: not a symmetric tensor of this communicator")
+            recs = [hit[0]]
+        self._ar_drain()
+        self.Barrier()  # no member is still inside an all-reduce on it
+        for rec in recs:
+            self._sym.remove(rec)
+            for k, st in list(self._ar_stage.items()):
+                if st.data_ptr() == rec.lo:
+                    del self._ar_stage[k]
+            rec.win.Free()
+
+    def _win_ok(self, src: torch.Tensor, dst: torch.Tensor, op: Op) -> bool:
+        code, dt = _PR_OP_CODE.get(op), _PR_DTYPES.get(src.dtype)
+        if code is None or dt is None or self.Get_size() > 8 or self._rank == UNDEFINED or self._ar_off:
+            return False
+        if dst.dtype != src.dtype or dst.device != src.device or dst.numel() != src.numel():
+            return False
+        if src.is_cuda and src.device != _rt.device():
+            return False
+        return bool(native().peer_reduce_supported(code, dt))
+
+    def _ar_staging(self, kind: str) -> torch.Tensor:
+        st = self._ar_stage.get(kind)
+        if st is None:
+            nb = max(4096, int(float(os.environ.get("MPIT_AR_STAGE_MB", "32")) * (1 << 20))) & ~15
+            st = self._ar_stage[kind] = self.sym_alloc(nb, torch.uint8, device=(kind == "cuda"))
+        return st
+
+    def _ar_submit(self, src: torch.Tensor, dst: torch.Tensor, op: Op, keep=()) -> Request:
+        """Take a ticket in the communicator's all-reduce FIFO (on the caller's thread, so the
+        order is the call order on every rank). The ticket carries an event recorded on the
+        caller's current stream; the worker makes the communicator's own stream wait for it and
+        runs the blocking protocol there. Completion means complete for every stream.
+        None (on every member alike): the window path is off for this communicator, the caller
+        falls back to today's routing."""
+        import queue
+
+        kind = "cuda" if src.is_cuda else "cpu"
+        inplace = src.data_ptr() == dst.data_ptr()
+        hit = self._sym_find(src)
+        disjoint = inplace or src.data_ptr() + _nbytes(src) <= dst.data_ptr() or \
+            dst.data_ptr() + _nbytes(dst) <= src.data_ptr()
+        if hit is not None and inplace:
+            plan = ("direct", hit[0].win, hit[1])
+        elif hit is not None and disjoint and self._sym_find(dst) is None and \
+                _nbytes(src) <= native().ar_oneshot_bytes():
+            plan = ("oneshot", hit[0].win, hit[1])  # straight into the caller's destination
+        else:
+            st = self._ar_staging(kind)  # (created collectively, here on the caller's thread)
+            if self._ar_off:  # (agreed while creating it: a member cannot map the staging window)
+                return None
+            plan = ("staged", self._sym_find(st)[0].win, st)
+        ev = None
+        if kind == "cuda":
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(src.device))
+        req = Request(self, keep=keep, event=threading.Event())
+        if self._ar_thread is None:
+            self._ar_q = queue.Queue()
+            if _rt.device() is not None:
+                self._ar_stream = torch.cuda.Stream(_rt.device())
+            self._ar_thread = threading.Thread(target=self._ar_worker, args=(self._ar_q,), daemon=True,
+                                               name=f"mpit-allreduce-{self._ctx}")
+            self._ar_thread.start()
+        self._ar_count("window")
+        if plan[0] == "staged":
+            self._ar_count("window_staged")
+        self._ar_q.put((plan, src, dst, _PR_OP_CODE[op], _PR_DTYPES[src.dtype], ev, req))
+        return req
+
+    def _ar_worker(self, q):
+        if _rt.device() is not None:
+            torch.cuda.set_device(_rt.device())
+        while True:
+            item = q.get()
+            if item is None:
+                q.task_done()
+                return
+            req = item[-1]
+            try:
+                self._ar_exec(*item[:-1])
+            except BaseException as e:  # surfaced by Wait / Test
+                req._err = e
+            req._ev.set()
+            q.task_done()
+
+    def _ar_exec(self, plan, src, dst, code, dt, ev):
+        n, es = src.numel(), src.element_size()
+        if ev is None:
+            self._ar_run(plan, src, dst, code, dt, n, es, 0, None)
+            return
+        s = self._ar_stream
+        with torch.cuda.stream(s):
+            ev.wait(s)  # what the caller queued before the call, and nothing later
+            self._ar_run(plan, src, dst, code, dt, n, es, s.cuda_stream, s)
+
+    def _ar_run(self, plan, src, dst, code, dt, n, es, sptr, stream):
+        how, win = plan[0], plan[1]._w
+        if how == "direct":
+            ok = win.allreduce(plan[2], n, dt, code, sptr, 0, 0)
+        elif how == "oneshot":
+            ok = win.allreduce(plan[2], n, dt, code, sptr, 1, dst.data_ptr())
+        else:
+            stage = plan[2]
+            cap = stage.numel() // es
+            ok, i = True, 0
+            while ok and i < n:
+                m = min(cap, n - i)
+                sv = stage[: m * es].view(src.dtype)
+                sv.copy_(src[i: i + m])
+                ok = win.allreduce(0, m, dt, code, sptr, 0, 0)
+                dst[i: i + m].copy_(sv)
+                i += m
+            if stream is not None:
+                stream.synchronize()
+        if not ok:
+            # (not reachable through sym_alloc / sym_register: they agree on the capability and
+            # switch the communicator to the fallback before any ticket is taken)
+            raise RuntimeError("mpit: this window cannot run the peer-reduce all-reduce (member not mapped)")
+
+    def _ar_drain(self):
+        if self._ar_q is not None:
+            self._ar_q.join()
+
+    def _ar_stop(self):
+        if self._ar_thread is not None:
+            self._ar_q.put(None)
+            self._ar_thread.join()
+            self._ar_thread = self._ar_q = None
 
     def _bg(self, fn, keep=()) -> Request:
         req = Request(self, keep=keep)
+        with _coll_cv:
+            ticket = _coll_tickets[0]
+            _coll_tickets[0] += 1
 
         def run():
+            with _coll_cv:
+                _coll_cv.wait_for(lambda: _coll_tickets[1] == ticket)
             try:
-                with _coll_lock:
-                    fn()
+                fn()
             except BaseException as e:  # surfaced by Wait/Test
                 req._err = e
+            finally:
+                with _coll_cv:
+                    _coll_tickets[1] += 1
+                    _coll_cv.notify_all()
 
         th = threading.Thread(target=run, daemon=True)
         req._thread = th
@@ -1023,7 +1297,7 @@ class Comm:
         st = _rt.state()
         mine = torch.tensor([st.next_ctx], dtype=torch.int64)
         out = torch.zeros(1, dtype=torch.int64)
-        self.Allreduce(mine, out, MAX)
+        self.Allreduce(mine, out, MAX, algo="auto")  # (creating a window agrees on a context: never through one)
         ctx = int(out.item())
         st.next_ctx = ctx + 1
         return ctx * 2  # even: user p2p; ctx + 2^20: collectives
@@ -1061,6 +1335,10 @@ class Comm:
 
     def Free(self):
         self._pg = None
+        self._ar_stop()  # (drains the FIFO: no member is inside an all-reduce of ours after it)
+        for rec in self._sym:  # symmetric memory still registered, the staging buffers included
+            rec.win.Free()
+        self._sym, self._ar_stage = [], {}
 
     def Disconnect(self):
         self.Barrier()

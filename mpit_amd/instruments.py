@@ -91,26 +91,34 @@ def ps_pingpong(mib: float = 640.0, iters: int = 100, warmup: int = 3, servers: 
             "per_client": rs, "aggregate_GBps_bidir": round(sum(r["GBps_bidir"] for r in rs), 2)}
 
 
-def allreduce_time(megs: float = 10.0, iters: int = 10, host: bool = False) -> dict:
-    """Allreduce SUM of megs x 2^20 fp32 on every rank (HBM tensors ride RCCL when every rank
-    owns its GPU), then one Iallreduce with Test before / after Wait; checked for
-    correctness against a float64 reduction of one element."""
+def allreduce_time(megs: float = 10.0, iters: int = 10, host: bool = False, algo: Optional[str] = None,
+                   dtype: torch.dtype = torch.float32, inplace: bool = False) -> dict:
+    """Allreduce SUM of megs x 2^20 elements (fp32 unless ``dtype``) on every rank (HBM tensors
+    ride RCCL when every rank owns its GPU), then one Iallreduce with Test before / after Wait;
+    checked for correctness against a float64 reduction of one element. ``algo``: the path
+    (comm.py Allreduce; None reads MPIT_ALLREDUCE). The window path is timed as the trainer
+    uses it: in place on symmetric memory. ``inplace``: time the other paths in place too (the
+    buffer reduced over and over, as the window arm does), for a like-for-like comparison;
+    the default times ``x`` into a second buffer, which includes a full-size copy."""
     W = COMM_WORLD()
     dev = torch.device("cpu") if host or _rt.device() is None else _rt.device()
     n = int(megs * (1 << 20))
-    x = torch.rand(n, device=dev)
+    x = torch.rand(n, device=dev).to(dtype)
+    window = W.Get_size() > 1 and W._ar_algo(algo) == "window" and W._win_ok(x, x, SUM)
+    if window:
+        return _allreduce_time_window(W, x, iters, dev)
     ref = x.clone()
-    W.Allreduce(ref, ref, SUM)  # warm-up (communicator init)
+    W.Allreduce(ref, ref, SUM, algo=algo)  # warm-up (communicator init)
     _sync(dev)
     W.Barrier()
     t0 = time.perf_counter()
     for _ in range(iters):
-        W.Allreduce(x, ref, SUM)
+        W.Allreduce(ref if inplace else x, ref, SUM, algo=algo)
     _sync(dev)
     t_ar = (time.perf_counter() - t0) / iters
     W.Barrier()
     t0 = time.perf_counter()
-    req = W.Iallreduce(x, ref, SUM)
+    req = W.Iallreduce(x, ref, SUM, algo=algo)
     before = req.Test()
     req.Wait()
     after = req.Test()
@@ -118,11 +126,52 @@ def allreduce_time(megs: float = 10.0, iters: int = 10, host: bool = False) -> d
     t_iar = time.perf_counter() - t0
     tot = torch.zeros(1, dtype=torch.float64)
     W.Allreduce(torch.tensor([float(x[:1].double().item())], dtype=torch.float64), tot, SUM)
-    ok = abs(float(ref[0].item()) - float(tot.item())) <= 1e-4 * max(1.0, abs(float(tot.item())))
-    nb = n * 4
+    tol = 1e-4 if dtype in (torch.float32, torch.float64) else 2e-2
+    ok = abs(float(ref[0].item()) - float(tot.item())) <= tol * max(1.0, abs(float(tot.item())))
+    nb = n * x.element_size()
     size = W.Get_size()
     rccl = bool(dev.type == "cuda" and W._use_rccl(x))
     return {"MiB": nb / (1 << 20), "ranks": size, "device": str(dev), "backend": "rccl" if rccl else "mpit-p2p",
+            "allreduce_ms": round(1000 * t_ar, 3), "iallreduce_ms": round(1000 * t_iar, 3),
+            "busbw_GBps": round(2 * (size - 1) / size * nb / t_ar / 1e9, 2) if size > 1 else None,
+            "test_before_wait": bool(before), "test_after_wait": bool(after), "correct": ok}
+
+
+def _allreduce_time_window(W, x: torch.Tensor, iters: int, dev) -> dict:
+    """The window path of :func:`allreduce_time` (same keys): in place on a symmetric buffer.
+    The timed calls reduce the buffer over and over (values grow by the rank count per call,
+    harmless for the few iterations of a timing run); it is restored from ``x`` for the check."""
+    n, size = x.numel(), W.Get_size()
+    buf = W.sym_alloc(n, x.dtype, device=dev.type == "cuda")
+    buf.copy_(x)
+    W.Allreduce(buf, buf, SUM, algo="window")  # warm-up (worker thread, stream)
+    _sync(dev)
+    buf.copy_(x)
+    _sync(dev)
+    W.Barrier()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        W.Allreduce(buf, buf, SUM, algo="window")
+    _sync(dev)
+    t_ar = (time.perf_counter() - t0) / iters
+    W.Barrier()
+    buf.copy_(x)
+    _sync(dev)
+    W.Barrier()  # (every member restored before any member's next call reads it)
+    t0 = time.perf_counter()
+    req = W.Iallreduce(buf, buf, SUM, algo="window")
+    before = req.Test()
+    req.Wait()
+    after = req.Test()
+    _sync(dev)
+    t_iar = time.perf_counter() - t0
+    tot = torch.zeros(1, dtype=torch.float64)
+    W.Allreduce(torch.tensor([float(x[:1].double().item())], dtype=torch.float64), tot, SUM, algo="auto")
+    tol = 1e-4 if x.dtype in (torch.float32, torch.float64) else 2e-2
+    ok = abs(float(buf[0].item()) - float(tot.item())) <= tol * max(1.0, abs(float(tot.item())))
+    nb = n * x.element_size()
+    W.sym_free(buf)
+    return {"MiB": nb / (1 << 20), "ranks": size, "device": str(dev), "backend": "mpit-window",
             "allreduce_ms": round(1000 * t_ar, 3), "iallreduce_ms": round(1000 * t_iar, 3),
             "busbw_GBps": round(2 * (size - 1) / size * nb / t_ar / 1e9, 2) if size > 1 else None,
             "test_before_wait": bool(before), "test_after_wait": bool(after), "correct": ok}

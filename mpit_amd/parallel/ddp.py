@@ -29,6 +29,20 @@ parameter, no memset of the flat gradient per step.
 ``wire="bf16"``: each bucket is cast into a bf16 mirror of the flat gradient and reduced in
 bf16 (half the bytes on every xGMI link), then cast back into the fp32 gradient at
 ``finish()``; the sum of the N gradients is rounded to bf16 once per ring step.
+
+``algo="window"`` (or ``MPIT_ALLREDUCE=window``; ``None`` reads the variable): the buckets are
+reduced by the peer-reduce kernel over symmetric memory (comm.py "window all-reduce"). On HBM
+the flat gradient (and the bf16 mirror) is registered once, here, so every bucket is an
+in-place byte range of one window: no staging, no copies, one launch per rank and bucket. The
+sum is the left fold in rank order whatever the bucket layout, rounded once on the bf16 wire.
+Hazards the protocol covers:
+* buckets are disjoint ranges, so peers pushing bucket b never touch ranges the side stream
+  (or the backward) is still filling for another bucket;
+* a bucket's all-reduce starts only after an event recorded behind its last producer, and
+  every member's input is complete at its first barrier;
+* ``finish()`` returns only after the second barrier of every bucket, so the next backward
+  cannot overwrite memory a peer is still reading, nor read a slice that has not landed.
+Host gradients (the CPU tier) cannot be exposed in place and go through the staging buffer.
 """
 from __future__ import annotations
 
@@ -42,7 +56,7 @@ from ..utils.flat import FlatParams
 
 class BucketedAllreduce:
     def __init__(self, model: torch.nn.Module, flat: FlatParams, bucket_mb: float = 25.0, comm: Optional[Comm] = None,
-                 first_bucket_mb: float = 4.0, wire: str = "fp32", steal: bool = False):
+                 first_bucket_mb: float = 4.0, wire: str = "fp32", steal: bool = False, algo: Optional[str] = None):
         if wire not in ("fp32", "bf16"):
             raise ValueError(f"BucketedAllreduce: wire must be fp32 or bf16, not {wire!r}")
         self.comm = comm or COMM_WORLD()
@@ -51,6 +65,13 @@ class BucketedAllreduce:
         self.members: List[List[int]] = []  # parameter indices per bucket (steal mode)
         self.wire = wire
         self.wbuf = torch.empty(flat.numel, dtype=torch.bfloat16, device=flat.grad.device) if wire == "bf16" else None
+        self.algo = self.comm._ar_algo(algo)
+        self._registered = []
+        if self.algo == "window" and self.comm.Get_size() > 1 and flat.grad.is_cuda and \
+                self.comm._win_ok(flat.grad, flat.grad, SUM):
+            for t in (flat.grad, self.wbuf):
+                if t is not None:
+                    self._registered.append(self.comm.sym_register(t))
         es = flat.grad.element_size()
         cap = int(bucket_mb * (1 << 20)) // es
         first = min(cap, int(first_bucket_mb * (1 << 20)) // es) if first_bucket_mb > 0 else cap
@@ -134,7 +155,7 @@ class BucketedAllreduce:
             seg16 = self.wbuf[lo:hi]
             seg16.copy_(seg)  # cast on the compute stream, ordered before the collective
             seg = seg16
-        self.reqs[b] = self.comm.Iallreduce(seg, seg, SUM)
+        self.reqs[b] = self.comm.Iallreduce(seg, seg, SUM, algo=self.algo)
 
     def finish(self):
         """Launch buckets whose parameters got no gradient, then wait for all."""
@@ -153,3 +174,11 @@ class BucketedAllreduce:
         for h in self._hooks:
             h.remove()
         self._hooks = []
+        self.release()
+
+    def release(self):
+        """Collective, like the construction: give back the windows registered on the flat
+        gradient (and the bf16 mirror). Later all-reduces go through the staging buffer."""
+        for t in self._registered:
+            self.comm.sym_free(t)
+        self._registered = []

@@ -57,6 +57,7 @@ class TrainConfig:
     server_rule: Optional[ServerOpt] = None
     seed: int = 1234
     bucket_mb: float = 25.0  # allreduce bucket size (parallel/ddp.py sizing note)
+    ar_algo: Optional[str] = None  # allreduce path: auto | window | p2p; None reads MPIT_ALLREDUCE
     extra: dict = field(default_factory=dict)
 
 
@@ -120,7 +121,8 @@ class Trainer:
                 cfg.extra.get("steal_grads", True)
             bmb = cfg.bucket_mb if self.world > 1 else float(1 << 20)
             self.ddp = BucketedAllreduce(self.model, self.flat, bucket_mb=bmb, wire=cfg.wire_dtype,
-                                         first_bucket_mb=4.0 if self.world > 1 else 0.0, steal=self.ar_steal)
+                                         first_bucket_mb=4.0 if self.world > 1 else 0.0, steal=self.ar_steal,
+                                         algo=cfg.ar_algo)
         else:
             self._start_ps()
         # Downpour su=1 on the GPU: let autograd hand over its gradient tensors and gather
@@ -494,6 +496,8 @@ class Trainer:
             self.ps_server.wait_done()
 
     def stop(self):
+        if self.ddp is not None:
+            self.ddp.release()  # (collective: every rank of a sync-DP job stops its trainer)
         if self.pc is not None:
             self.pc.stop()
         if self.ps_server is not None:
