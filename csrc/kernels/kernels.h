@@ -140,8 +140,10 @@ void bn_pair_bwd_apply(int dev, hipStream_t s, uintptr_t dy, uintptr_t mask, uin
 // for fp32 ones in an f32 call; ReLU bit masks are one byte per 8 channels either way.
 // C[M,N] (bf16) = A[M,K] . B[N,K]^T; optional per-column (mean, M2) partials of C per
 // 128-row tile into stats[ceil(M/128)][2][N] (gemm_nt_stats_floats); optional bf16 cin
-// [M, ldc] added to the product before rounding (may alias C); optional cmask (with cin,
-// ldc == N): the bn_act ReLU bit mask of cin (1 byte / 8 channels) — adds cin*mask.
+// [M, ldc] (may alias C): the product is rounded to bf16 first, then cin is added and the sum
+// rounded again — C = bf16(bf16(A.B^T) + cin), not bf16(A.B^T + cin) (fp32 calls: a single
+// fp32 add); optional cmask (with cin, ldc == N): the bn_act ReLU bit mask of cin (1 byte /
+// 8 channels) — adds cin*mask.
 // Optional red: C is the output gradient of a bn_act layer (x, mask, mean its forward
 // input / ReLU mask / batch mean, [.., N] like C): the GEMM also writes that layer's
 // backward reduction partials (sum dz, sum dz*(x-mean)), dz = C*mask, one row pair per
