@@ -257,7 +257,8 @@ __device__ __forceinline__ void mask_store(uint8_t* __restrict__ m, const Slot<S
 // nothing waits on it) into slot blockIdx % kBoundSlots of the bound (kernels.h; one address
 // took 4096 serialised atomics per pass: +20 us a call), which the kernel that ran before the apply on the same
 // stream set to zero — the finalize that wrote the apply coefficients (FinArgs::zero, the
-// GEMM's folded finalize: EpiArgs::fzero) or, on the paths without one, a 4-byte memset.
+// GEMM's folded finalize: EpiArgs::fzero; the slot floats only) or, on the paths without one, a
+// memset of all kBoundFloats floats.
 // |out| >= 0, so the float bits order like unsigned integers.
 struct AmaxOut {
   float* amax;  // null: not wanted

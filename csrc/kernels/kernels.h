@@ -102,8 +102,11 @@ void bn_act_fwd(int dev, hipStream_t s, bool bf16, uintptr_t x, uintptr_t res, u
                 uintptr_t save_rstd, uintptr_t ws, float momentum, float eps, bool relu, uintptr_t mask,
                 uintptr_t stats = 0, int64_t nstat = 0, uintptr_t amax = 0, uintptr_t coef = 0,
                 const PlaneSpec* planes = nullptr);
-// amax (optional, fp32 [1]): max |y| over the tensor (bn_act_bwd: max |dx|), the scale bound of the
-// fp16x3 GEMMs that read it: zeroed by this call's finalize, raised by its apply pass. With
+// amax (optional, fp32 [kBoundFloats], the slotted bound described at BnRed below): max |y| over
+// the tensor (bn_act_bwd: max |dx|), taken from the fp32 values before a bf16 store rounds them,
+// the scale bound of the fp16x3 GEMMs that read it: zeroed by this call's finalize (the tile
+// finalize zeroes the kBoundSlots slot floats only, the stand-alone passes memset all
+// kBoundFloats), raised by its apply pass with one atomic max per block, never lowered. With
 // y / dx null (the coefficient-only calls of a bn_pair) amax is only zeroed, for the pair
 // apply that follows. Given coefficients (bn_act_bwd coef), the GEMM that folded the finalize
 // zeroed it (BnRed::fzero).
