@@ -331,6 +331,27 @@ PYBIND11_MODULE(_mpit, m) {
          uintptr_t loss, uintptr_t d) { softmax_xent(dev, S(s), rows, C, x, ldx, bf16, tgt, scale, loss, d); },
       py::arg("dev"), py::arg("stream"), py::arg("rows"), py::arg("C"), py::arg("x"), py::arg("ldx"),
       py::arg("bf16"), py::arg("tgt"), py::arg("scale"), py::arg("loss"), py::arg("d"));
+  m.def(
+      "seq_hidden_windows",
+      [](int dev, uintptr_t s, uintptr_t tok, int64_t B, int T, uintptr_t E, int D, uintptr_t Wh, uintptr_t bh, int H,
+         int k, uintptr_t out, int Kp) { seq_hidden_windows(dev, S(s), tok, B, T, E, D, Wh, bh, H, k, out, Kp); },
+      py::arg("dev"), py::arg("stream"), py::arg("tok"), py::arg("B"), py::arg("T"), py::arg("E"), py::arg("D"),
+      py::arg("Wh"), py::arg("bh"), py::arg("H"), py::arg("k"), py::arg("out"), py::arg("Kp"));
+  m.def(
+      "seq_max_norm",
+      [](int dev, uintptr_t s, uintptr_t c, int64_t ldc, uintptr_t tok, int64_t B, int T, int k, int64_t pad_idx,
+         uintptr_t bias, int F, float eps, uintptr_t out) {
+        seq_max_norm(dev, S(s), c, ldc, tok, B, T, k, pad_idx, bias, F, eps, out);
+      },
+      py::arg("dev"), py::arg("stream"), py::arg("c"), py::arg("ldc"), py::arg("tok"), py::arg("B"), py::arg("T"),
+      py::arg("k"), py::arg("pad_idx"), py::arg("bias"), py::arg("F"), py::arg("eps"), py::arg("out"));
+  m.def(
+      "gesd_gather",
+      [](int dev, uintptr_t s, uintptr_t q, uintptr_t cand, uintptr_t idx, int64_t n, int w, int D, uintptr_t out) {
+        gesd_gather(dev, S(s), q, cand, idx, n, w, D, out);
+      },
+      py::arg("dev"), py::arg("stream"), py::arg("q"), py::arg("cand"), py::arg("idx"), py::arg("n"), py::arg("w"),
+      py::arg("D"), py::arg("out"));
   m.def("relu_bias_bwd_ws_floats", &relu_bias_bwd_ws_floats);
   m.def(
       "relu_bias_bwd",

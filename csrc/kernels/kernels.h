@@ -249,6 +249,23 @@ void conv_dgrad_strided(int dev, hipStream_t s, int Nb, int H, int W, int C, int
 // loss (fp32 [rows]) and the logits' gradient d = (softmax - onehot) * scale (fp32 [rows][C])
 void softmax_xent(int dev, hipStream_t s, int64_t rows, int C, uintptr_t x, int64_t ldx, bool bf16, uintptr_t tgt,
                   float scale, uintptr_t loss, uintptr_t d);
+
+// ---- BiCNN sentence encoder and GESD scoring, forward only, fp32, device only (seq.hip) ----
+// tok int64 [B][T] (ids trusted), E [V][D], Wh [H][D], bh [H] or 0 -> out fp32 [B*T][Kp], the im2col
+// rows of a width-k temporal convolution: out[(b,t)][j*H + i] = tanh(bh[i] + E[tok[b][t+j]] . Wh[i])
+// for t + j < T; missing taps and columns k*H .. Kp-1 are 0. Tap j of row (b,t) is bitwise tap 0
+// of row (b,t+j).
+void seq_hidden_windows(int dev, hipStream_t s, uintptr_t tok, int64_t B, int T, uintptr_t E, int D, uintptr_t Wh,
+                        uintptr_t bh, int H, int k, uintptr_t out, int Kp);
+// c fp32 [B*T][ldc >= F] (the convolution GEMM's output) -> out fp32 [B][F]: m = max(0, bias[f] +
+// max over the valid windows t (t <= T-k and tok[b][t+k-1] != pad_idx) of c[(b,t)][f]), 0 without
+// a valid window; out = m / max(|m|_2, eps). bias [F] or 0. The same bits for a sentence in any batch.
+void seq_max_norm(int dev, hipStream_t s, uintptr_t c, int64_t ldc, uintptr_t tok, int64_t B, int T, int k,
+                  int64_t pad_idx, uintptr_t bias, int F, float eps, uintptr_t out);
+// q [n][D], cand [m][D], idx int64 [n][w] (trusted) -> out fp32 [n][w], the GESD similarity of q[r]
+// and cand[idx[r][c]]: 1 / (1 + |a - b|_2) * 1 / (1 + exp(-(a . b + 1))). Independent of n and w.
+void gesd_gather(int dev, hipStream_t s, uintptr_t q, uintptr_t cand, uintptr_t idx, int64_t n, int w, int D,
+                 uintptr_t out);
 int64_t relu_bias_bwd_ws_floats(int C);
 // out[c] = sum over rows k < nb of part[k * ld + c] (fp32, fixed order: deterministic); mid:
 // col_sums_ws_floats(C) floats of workspace (needed when nb > 64)

@@ -147,6 +147,9 @@ def build_args(argv=None):
     f("binaryDir", default=".", help="-preloadBinary: directory of the reference's Torch7 caches (binary_map*)")
     f("save", default="bicnn_out")
     f("synthetic", type=int, default=200, help="synthetic answers when no data files are given")
+    # opt-in: the encodes / scorings without autograd (negative-sampling scan, tester) on the
+    # forward-only HIP kernels (ops/seq.py); default: MPIT_BICNN_FUSED, else off
+    f("fusedEncoder", action="store_true", default=None)
     a = ap.parse_args(argv)
     if a.mva == 0.0:
         a.mva = a.movingrate
@@ -207,7 +210,7 @@ def evaluate(model, data, items, dev, max_q=0) -> float:
         eq = model.encode(pad_batch([q for _, q, _ in chunk]).to(dev))
         for (labels, _, pool), e in zip(chunk, eq):
             cand = torch.tensor([pos[p] for p in pool], device=dev)
-            sims = gesd(e.unsqueeze(0).expand(len(pool), -1), emb[cand])
+            sims = model.score(e.unsqueeze(0), emb, cand.unsqueeze(0))[0]
             best = len(pool) - 1 - int(sims.flip(0).argmax())  # last maximum
             correct += int(pool[best] in labels)
             total += 1
@@ -294,7 +297,8 @@ def main(argv=None) -> int:
     torch.manual_seed(rank)
     data = load_data(a)  # servers too: the shard sizes follow the vocabulary
     torch.manual_seed(1)  # identical initial weights
-    model = BiCNN(len(data.word2idx), a.embeddingDim, a.wordHiddenDim, a.numFilters, a.contConvWidth, a.mmode).to(dev)
+    model = BiCNN(len(data.word2idx), a.embeddingDim, a.wordHiddenDim, a.numFilters, a.contConvWidth, a.mmode,
+                  fused=a.fusedEncoder).to(dev)
     with torch.no_grad():
         model.embed.weight.copy_(data.embedding_matrix().to(dev))
     flat = FlatParams(model)
@@ -340,6 +344,11 @@ def main(argv=None) -> int:
             train(a, rank, model, flat, plong, data, dev, pc, log, ev, cranks)
             for t in testers:
                 W.Send(torch.ones(1, dtype=torch.int64), t, TAG_WORKER_DONE)
+        if model.fused:  # which path the encodes / scorings without autograd took on this rank
+            from mpit_amd.ops.seq import COUNTERS
+
+            print(f"[bicnn rank {rank}] fused encoder: " + " ".join(f"{k}={v}" for k, v in COUNTERS.items()),
+                  flush=True)
         pc.stop()
         log.close()
     if server is not None and rank in cranks:

@@ -14,8 +14,16 @@ sampling keeps the reference's semantics — per example, the first margin-viola
 within ``maxnegsample`` (:func:`first_violations`, BiCNN/bicnn.lua:321-374) — with the
 draws encoded in batched windows; :func:`margin_ranking_loss` is the cheaper
 hardest-of-k alternative.
+
+``fused`` (opt-in: ``BiCNN(fused=True)``, MPIT_BICNN_FUSED=1, apps/bicnn.py -fusedEncoder): the
+encodes and scorings that run without autograd on the GPU (the scan above, the tester) take the
+forward-only HIP kernels of ops/seq.py, whose per-sentence result does not depend on the batch;
+everything under autograd or vmap, and every call with the switch off, is the PyTorch code below.
 """
 from __future__ import annotations
+
+import os
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -56,8 +64,11 @@ def gesd(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
 
 class BiCNN(nn.Module):
     def __init__(self, vocab: int = 22354, emb_dim: int = 100, hidden: int = 200, filters: int = 3000,
-                 conv_width: int = 2, mmode: int = 1, pad_idx: int = 0):
+                 conv_width: int = 2, mmode: int = 1, pad_idx: int = 0, fused: Optional[bool] = None):
         super().__init__()
+        if fused is None:
+            fused = os.environ.get("MPIT_BICNN_FUSED", "0") not in ("", "0")
+        self.fused = bool(fused)
         self.embed = nn.Embedding(vocab, emb_dim, padding_idx=pad_idx)
         self.hidden = nn.Linear(emb_dim, hidden)
         self.conv = nn.Conv1d(hidden, filters, conv_width)
@@ -65,8 +76,34 @@ class BiCNN(nn.Module):
         self.mmode = mmode
         self.pad_idx = pad_idx
 
+    def fused_ok(self, t: torch.Tensor) -> bool:
+        """The forward-only kernels of ops/seq.py apply to a call on ``t``: the switch is on, the
+        tensor is on the GPU, nothing records gradients or autocasts, the parameters are
+        contiguous fp32 and the native module loads."""
+        if not (self.fused and t.is_cuda and t.numel() > 0 and not torch.is_grad_enabled()
+                and not torch.is_autocast_enabled("cuda")):
+            return False
+        ps = (self.embed.weight, self.hidden.weight, self.hidden.bias, self.conv.weight, self.conv.bias)
+        if any(p.dtype != torch.float32 or p.device != t.device for p in ps):
+            return False
+        if not all(p.is_contiguous() for p in ps if p is not self.conv.weight) or self.norm.p != 2:
+            return False
+        try:
+            from .._ext import native
+
+            native()
+        except ImportError:
+            return False
+        return True
+
     def encode(self, tok: torch.Tensor) -> torch.Tensor:
         """tok: [B, T] word ids (pad_idx = padding) -> [B, filters] unit embeddings."""
+        if self.fused:
+            from ..ops import seq
+
+            if tok.dim() == 2 and tok.dtype == torch.int64 and self.fused_ok(tok):
+                return seq.encode(self, tok)
+            seq.COUNTERS["encode_fallback"] += 1
         h = torch.tanh(self.hidden(self.embed(tok)))  # [B, T, H]
         c = self.conv(h.transpose(1, 2))  # [B, F, T-k+1]
         k = self.conv.kernel_size[0]
@@ -79,6 +116,20 @@ class BiCNN(nn.Module):
         m = c.max(dim=-1).values
         m = torch.nan_to_num(m, neginf=0.0)
         return self.norm(F.relu(m))
+
+    def score(self, eq: torch.Tensor, emb: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+        """GESD of every ``eq[r]`` [n, F] with the rows ``emb[idx[r]]`` of ``emb`` [m, F]
+        (``idx`` [n, w] int64) -> [n, w]."""
+        if self.fused:
+            from ..ops import seq
+
+            if (eq.dtype == torch.float32 and emb.dtype == torch.float32 and idx.dtype == torch.int64
+                    and emb.device == eq.device and idx.device == eq.device and self.fused_ok(eq)
+                    and eq.is_contiguous() and emb.is_contiguous() and idx.numel() > 0):
+                seq.COUNTERS["gesd_fused"] += 1
+                return seq.gesd_gather(eq, emb, idx.contiguous())
+            seq.COUNTERS["gesd_fallback"] += 1
+        return gesd(eq.unsqueeze(1).expand(-1, idx.shape[1], -1), emb[idx])
 
     def forward(self, q, a_pos, a_neg):
         eq = self.encode(q)
@@ -145,7 +196,7 @@ def first_violations(model: "BiCNN", eq: torch.Tensor, s_pos: torch.Tensor, draw
         idx = torch.tensor([[row[x] for x in s] + [0] * (w - len(s)) for s in seqs], device=dev)
         valid = torch.tensor([[1] * len(s) + [0] * (w - len(s)) for s in seqs], device=dev, dtype=torch.bool)
         li = torch.tensor(live, device=dev)
-        sn = gesd(eq[li].unsqueeze(1).expand(-1, w, -1), emb[idx])  # [n_live, w]
+        sn = model.score(eq[li], emb, idx)  # [n_live, w]
         viol = ((s_pos[li].unsqueeze(1) - sn) < margin) & valid
         has = viol.any(1).tolist()
         first = viol.to(torch.int32).argmax(1).tolist()
