@@ -352,6 +352,55 @@ PYBIND11_MODULE(_mpit, m) {
       },
       py::arg("dev"), py::arg("stream"), py::arg("q"), py::arg("cand"), py::arg("idx"), py::arg("n"), py::arg("w"),
       py::arg("D"), py::arg("out"));
+  m.def(
+      "seq_max_norm_arg",
+      [](int dev, uintptr_t s, uintptr_t c, int64_t ldc, uintptr_t tok, int64_t B, int T, int k, int64_t pad_idx,
+         uintptr_t bias, int F, float eps, uintptr_t out, uintptr_t arg, uintptr_t den) {
+        seq_max_norm_arg(dev, S(s), c, ldc, tok, B, T, k, pad_idx, bias, F, eps, out, arg, den);
+      },
+      py::arg("dev"), py::arg("stream"), py::arg("c"), py::arg("ldc"), py::arg("tok"), py::arg("B"), py::arg("T"),
+      py::arg("k"), py::arg("pad_idx"), py::arg("bias"), py::arg("F"), py::arg("eps"), py::arg("out"), py::arg("arg"),
+      py::arg("den"));
+  m.def(
+      "gesd_pair_bwd",
+      [](int dev, uintptr_t s, uintptr_t y, int64_t n, int F, float margin, uintptr_t err, uintptr_t sc,
+         uintptr_t gy) { gesd_pair_bwd(dev, S(s), y, n, F, margin, err, sc, gy); },
+      py::arg("dev"), py::arg("stream"), py::arg("y"), py::arg("n"), py::arg("F"), py::arg("margin"), py::arg("err"),
+      py::arg("sc"), py::arg("gy"));
+  m.def(
+      "seq_norm_max_bwd",
+      [](int dev, uintptr_t s, uintptr_t gy, uintptr_t y, uintptr_t arg, uintptr_t den, int64_t Sn, int T, int F,
+         int Fp, float eps, uintptr_t dm, uintptr_t dc) {
+        seq_norm_max_bwd(dev, S(s), gy, y, arg, den, Sn, T, F, Fp, eps, dm, dc);
+      },
+      py::arg("dev"), py::arg("stream"), py::arg("gy"), py::arg("y"), py::arg("arg"), py::arg("den"), py::arg("S"),
+      py::arg("T"), py::arg("F"), py::arg("Fp"), py::arg("eps"), py::arg("dm"), py::arg("dc"));
+  m.def(
+      "seq_conv_wgrad_pe",
+      [](int dev, uintptr_t s, uintptr_t dm, uintptr_t arg, uintptr_t win, int64_t n, int T, int F, int H, int k,
+         int Kp, uintptr_t g, int64_t ldg, int64_t offW, int64_t offB) {
+        seq_conv_wgrad_pe(dev, S(s), dm, arg, win, n, T, F, H, k, Kp, g, ldg, offW, offB);
+      },
+      py::arg("dev"), py::arg("stream"), py::arg("dm"), py::arg("arg"), py::arg("win"), py::arg("n"), py::arg("T"),
+      py::arg("F"), py::arg("H"), py::arg("k"), py::arg("Kp"), py::arg("g"), py::arg("ldg"), py::arg("offW"),
+      py::arg("offB"));
+  m.def(
+      "seq_hidden_bwd",
+      [](int dev, uintptr_t s, uintptr_t dwin, int64_t ldw, uintptr_t win, int Kp, int64_t Sn, int T, int H, int k,
+         uintptr_t Wh, int D, uintptr_t da, uintptr_t de) {
+        seq_hidden_bwd(dev, S(s), dwin, ldw, win, Kp, Sn, T, H, k, Wh, D, da, de);
+      },
+      py::arg("dev"), py::arg("stream"), py::arg("dwin"), py::arg("ldw"), py::arg("win"), py::arg("Kp"), py::arg("S"),
+      py::arg("T"), py::arg("H"), py::arg("k"), py::arg("Wh"), py::arg("D"), py::arg("da"), py::arg("de"));
+  m.def(
+      "seq_hidden_embed_grad_pe",
+      [](int dev, uintptr_t s, uintptr_t da, uintptr_t de, uintptr_t tok, uintptr_t E, int64_t V, int64_t n, int T,
+         int H, int D, int64_t pad_idx, uintptr_t g, int64_t ldg, int64_t offE, int64_t offWh, int64_t offBh) {
+        seq_hidden_embed_grad_pe(dev, S(s), da, de, tok, E, V, n, T, H, D, pad_idx, g, ldg, offE, offWh, offBh);
+      },
+      py::arg("dev"), py::arg("stream"), py::arg("da"), py::arg("de"), py::arg("tok"), py::arg("E"), py::arg("V"),
+      py::arg("n"), py::arg("T"), py::arg("H"), py::arg("D"), py::arg("pad_idx"), py::arg("g"), py::arg("ldg"),
+      py::arg("offE"), py::arg("offWh"), py::arg("offBh"));
   m.def("relu_bias_bwd_ws_floats", &relu_bias_bwd_ws_floats);
   m.def(
       "relu_bias_bwd",

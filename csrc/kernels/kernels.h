@@ -266,6 +266,37 @@ void seq_max_norm(int dev, hipStream_t s, uintptr_t c, int64_t ldc, uintptr_t to
 // and cand[idx[r][c]]: 1 / (1 + |a - b|_2) * 1 / (1 + exp(-(a . b + 1))). Independent of n and w.
 void gesd_gather(int dev, hipStream_t s, uintptr_t q, uintptr_t cand, uintptr_t idx, int64_t n, int w, int D,
                  uintptr_t out);
+
+// ---- BiCNN per-example gradients of the margin loss, fp32, device only (seq_grad.hip) ----
+// S = 3n sentences [q; a_pos; a_neg] of a common T; sentence s belongs to example s % n. g is the
+// [n][ldg] per-example gradient matrix, off* the parameters' offsets in a row (biases: -1 = none).
+// Every reduction order is fixed by F, H, D, k and the example's own tokens.
+// seq_max_norm + arg int32 [B][F] (the first valid window attaining the max; -1 without a valid
+// window or with a ReLU output of 0) and den fp32 [B] (the clamped norm). out: seq_max_norm's bits.
+void seq_max_norm_arg(int dev, hipStream_t s, uintptr_t c, int64_t ldc, uintptr_t tok, int64_t B, int T, int k,
+                      int64_t pad_idx, uintptr_t bias, int F, float eps, uintptr_t out, uintptr_t arg, uintptr_t den);
+// y [3n][F] -> sc [2][n] (sp = gesd(y[k], y[n+k]), sn = gesd(y[k], y[2n+k]): gesd_gather's bits),
+// err [n] = max(0, (margin - sp) + sn), gy [3n][F] = d err / d y (zeros where err == 0).
+void gesd_pair_bwd(int dev, hipStream_t s, uintptr_t y, int64_t n, int F, float margin, uintptr_t err, uintptr_t sc,
+                   uintptr_t gy);
+// dm [S][F] = arg >= 0 ? (gy - y * sum_f(gy * y)) / den : 0, and ALL of dc [S*T][Fp] (16-byte
+// aligned, Fp % 4 == 0): dm[s][f] at row (s, arg[s][f]), zero elsewhere (pad columns included).
+void seq_norm_max_bwd(int dev, hipStream_t s, uintptr_t gy, uintptr_t y, uintptr_t arg, uintptr_t den, int64_t S, int T,
+                      int F, int Fp, float eps, uintptr_t dm, uintptr_t dc);
+// g[k][offW + (f*H + i)*k + j] = sum over s = k, n+k, 2n+k (arg >= 0 only) of dm[s][f] *
+// win[(s, arg[s][f])][j*H + i]; g[k][offB + f] = the sum of the three dm. win [S*T][Kp].
+void seq_conv_wgrad_pe(int dev, hipStream_t s, uintptr_t dm, uintptr_t arg, uintptr_t win, int64_t n, int T, int F,
+                       int H, int k, int Kp, uintptr_t g, int64_t ldg, int64_t offW, int64_t offB);
+// da [S*T][H] = (1 - win[(s,t)][i]^2) * sum_{j<k, j<=t} dwin[(s,t-j)][j*H + i] (dwin [S*T][ldw]) and
+// de [S*T][D] = Wh^T da per token.
+void seq_hidden_bwd(int dev, hipStream_t s, uintptr_t dwin, int64_t ldw, uintptr_t win, int Kp, int64_t S, int T, int H,
+                    int k, uintptr_t Wh, int D, uintptr_t da, uintptr_t de);
+// Over example k's tokens in the order q, a_pos, a_neg, ascending t: g[k][offWh + i*D + d] = sum da[i] *
+// E[tok][d], g[k][offBh + i] = sum da[i], g[k][offE + v*D + d] = sum of de over the occurrences of
+// word v != pad_idx (each touched row written once; other rows of g are left alone). E [V][D].
+void seq_hidden_embed_grad_pe(int dev, hipStream_t s, uintptr_t da, uintptr_t de, uintptr_t tok, uintptr_t E,
+                              int64_t V, int64_t n, int T, int H, int D, int64_t pad_idx, uintptr_t g, int64_t ldg,
+                              int64_t offE, int64_t offWh, int64_t offBh);
 int64_t relu_bias_bwd_ws_floats(int C);
 // out[c] = sum over rows k < nb of part[k * ld + c] (fp32, fixed order: deterministic); mid:
 // col_sums_ws_floats(C) floats of workspace (needed when nb > 64)

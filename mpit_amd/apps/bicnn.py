@@ -150,6 +150,9 @@ def build_args(argv=None):
     # opt-in: the encodes / scorings without autograd (negative-sampling scan, tester) on the
     # forward-only HIP kernels (ops/seq.py); default: MPIT_BICNN_FUSED, else off
     f("fusedEncoder", action="store_true", default=None)
+    # opt-in: the parity rule's per-example gradients on the forward + backward HIP kernels of
+    # ops/seq.py instead of torch.func.vmap; default: MPIT_BICNN_FUSED_GRAD, else off
+    f("fusedGrad", action="store_true", default=None)
     a = ap.parse_args(argv)
     if a.mva == 0.0:
         a.mva = a.movingrate
@@ -298,7 +301,7 @@ def main(argv=None) -> int:
     data = load_data(a)  # servers too: the shard sizes follow the vocabulary
     torch.manual_seed(1)  # identical initial weights
     model = BiCNN(len(data.word2idx), a.embeddingDim, a.wordHiddenDim, a.numFilters, a.contConvWidth, a.mmode,
-                  fused=a.fusedEncoder).to(dev)
+                  fused=a.fusedEncoder, fused_grad=a.fusedGrad).to(dev)
     with torch.no_grad():
         model.embed.weight.copy_(data.embedding_matrix().to(dev))
     flat = FlatParams(model)
@@ -347,8 +350,13 @@ def main(argv=None) -> int:
         if model.fused:  # which path the encodes / scorings without autograd took on this rank
             from mpit_amd.ops.seq import COUNTERS
 
-            print(f"[bicnn rank {rank}] fused encoder: " + " ".join(f"{k}={v}" for k, v in COUNTERS.items()),
-                  flush=True)
+            print(f"[bicnn rank {rank}] fused encoder: " + " ".join(
+                f"{k}={v}" for k, v in COUNTERS.items() if not k.startswith("pegrad_")), flush=True)
+        if model.fused_grad:  # which path the parity rule's per-example gradients took
+            from mpit_amd.ops.seq import COUNTERS
+
+            print(f"[bicnn rank {rank}] fused grad: " + " ".join(
+                f"{k}={v}" for k, v in COUNTERS.items() if k.startswith("pegrad_")), flush=True)
         pc.stop()
         log.close()
     if server is not None and rank in cranks:

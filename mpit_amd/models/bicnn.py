@@ -19,6 +19,11 @@ hardest-of-k alternative.
 encodes and scorings that run without autograd on the GPU (the scan above, the tester) take the
 forward-only HIP kernels of ops/seq.py, whose per-sentence result does not depend on the batch;
 everything under autograd or vmap, and every call with the switch off, is the PyTorch code below.
+
+``fused_grad`` (opt-in, independent of ``fused``: ``BiCNN(fused_grad=True)``, MPIT_BICNN_FUSED_GRAD=1,
+apps/bicnn.py -fusedGrad): :func:`parity_grad_` takes its per-example gradients and hinge values
+from ops/seq.py ``per_example_grads`` (the same forward kernels, bit for bit, and a hand-written
+backward that writes only the embedding rows an example touches) instead of torch.func.vmap.
 """
 from __future__ import annotations
 
@@ -64,11 +69,15 @@ def gesd(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
 
 class BiCNN(nn.Module):
     def __init__(self, vocab: int = 22354, emb_dim: int = 100, hidden: int = 200, filters: int = 3000,
-                 conv_width: int = 2, mmode: int = 1, pad_idx: int = 0, fused: Optional[bool] = None):
+                 conv_width: int = 2, mmode: int = 1, pad_idx: int = 0, fused: Optional[bool] = None,
+                 fused_grad: Optional[bool] = None):
         super().__init__()
         if fused is None:
             fused = os.environ.get("MPIT_BICNN_FUSED", "0") not in ("", "0")
         self.fused = bool(fused)
+        if fused_grad is None:
+            fused_grad = os.environ.get("MPIT_BICNN_FUSED_GRAD", "0") not in ("", "0")
+        self.fused_grad = bool(fused_grad)
         self.embed = nn.Embedding(vocab, emb_dim, padding_idx=pad_idx)
         self.hidden = nn.Linear(emb_dim, hidden)
         self.conv = nn.Conv1d(hidden, filters, conv_width)
@@ -80,8 +89,21 @@ class BiCNN(nn.Module):
         """The forward-only kernels of ops/seq.py apply to a call on ``t``: the switch is on, the
         tensor is on the GPU, nothing records gradients or autocasts, the parameters are
         contiguous fp32 and the native module loads."""
-        if not (self.fused and t.is_cuda and t.numel() > 0 and not torch.is_grad_enabled()
-                and not torch.is_autocast_enabled("cuda")):
+        if not (self.fused and not torch.is_grad_enabled()):
+            return False
+        return self._kernels_ok(t)
+
+    def fused_grad_ok(self, t: torch.Tensor) -> bool:
+        """The per-example gradient kernels of ops/seq.py apply to a call on ``t``: :meth:`fused_ok`'s
+        conditions with ``fused_grad`` for the switch and without the "grad disabled" one (they use
+        no autograd), and a plain stride-1 convolution."""
+        c = self.conv
+        if not self.fused_grad or c.stride != (1,) or c.padding != (0,) or c.dilation != (1,) or c.groups != 1:
+            return False
+        return self._kernels_ok(t)
+
+    def _kernels_ok(self, t: torch.Tensor) -> bool:
+        if not (t.is_cuda and t.numel() > 0 and not torch.is_autocast_enabled("cuda")):
             return False
         ps = (self.embed.weight, self.hidden.weight, self.hidden.bias, self.conv.weight, self.conv.bias)
         if any(p.dtype != torch.float32 or p.device != t.device for p in ps):
@@ -258,6 +280,26 @@ def parity_grad_(model: "BiCNN", flat, q, a_pos, a_neg, margin: float, l1: float
     G = flat.grad
     G.zero_()
     n = q.shape[0]
+    fused = False
+    if getattr(model, "fused_grad", False):
+        from ..ops import seq
+
+        fused = (n > 0 and all(t.dim() == 2 and t.dtype == torch.int64 and t.device == q.device
+                               for t in (q, a_pos, a_neg)) and model.fused_grad_ok(q))
+        if not fused:
+            seq.COUNTERS["pegrad_fallback"] += 1
+    if fused:  # forward and backward on the kernels of ops/seq.py; the hinge values come with them
+        errs = []
+        for s in range(0, n, chunk):
+            g, err = seq.per_example_grads(model, flat, q[s:s + chunk], a_pos[s:s + chunk], a_neg[s:s + chunk], margin)
+            ops.clamp_scan_(G, g, flat.flat[: flat.numel], l1, l2, clip)
+            errs.append(err)
+        with torch.no_grad():
+            loss = torch.cat(errs).sum()
+            if l1 or l2:
+                nm = ops.norms(flat.flat[: flat.numel])
+                loss = loss + n * (l1 * nm[0] + 0.5 * l2 * nm[1])
+        return loss
     for s in range(0, n, chunk):
         g = per_example_grads(model, flat, q[s:s + chunk], a_pos[s:s + chunk], a_neg[s:s + chunk], margin)
         ops.clamp_scan_(G, g, flat.flat[: flat.numel], l1, l2, clip)

@@ -16,7 +16,12 @@ layout transposes) -> masked_fill -> max -> nan_to_num -> relu -> normalise with
 and :func:`gesd_gather` scores gathered row pairs in one pass per pair. Every reduction runs
 in an order fixed by the row length, so a sentence's encoding and a pair's score are the same
 bits in any batch. fp32, device tensors only, no autograd: the callers (models/bicnn.py) keep
-PyTorch's path for everything else. ``COUNTERS`` tells which path ran."""
+PyTorch's path for everything else. ``COUNTERS`` tells which path ran.
+
+:func:`per_example_grads` (csrc/kernels/seq_grad.hip) is the forward-plus-backward counterpart for
+the parity rule (models/bicnn.py ``parity_grad_``, ``BiCNN(fused_grad=True)``): the same forward
+kernels, bit for bit, with the arg-max kept, then the per-example gradients of the margin loss
+written straight into the ``[n, flat.numel]`` matrix: no autograd, no dense embedding gradient."""
 from __future__ import annotations
 
 from typing import Optional
@@ -25,7 +30,8 @@ import torch
 
 from .._ext import native
 
-COUNTERS = {"encode_fused": 0, "encode_fallback": 0, "gesd_fused": 0, "gesd_fallback": 0}
+COUNTERS = {"encode_fused": 0, "encode_fallback": 0, "gesd_fused": 0, "gesd_fallback": 0,
+            "pegrad_fused": 0, "pegrad_fallback": 0}
 
 
 def _stream(t: torch.Tensor) -> int:
@@ -170,3 +176,123 @@ def encode(model, tok: torch.Tensor) -> torch.Tensor:
                    model.norm.eps)
     COUNTERS["encode_fused"] += 1
     return out
+
+
+def pack_conv_weight_t(weight: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Conv1d weight ``[F, H, k]`` -> ``WpT[Kp64, Fp]``, the transpose of :func:`pack_conv_weight`'s
+    ``Wp`` with its rows rounded up to 64 (``gemm_nt``'s N): ``WpT[j*H + i][f] = weight[f][i][j]``,
+    zero elsewhere. With ``out`` (a zero-initialised buffer whose pad stays untouched) one strided
+    copy refills it. Pure torch."""
+    F, H, k = weight.shape
+    Fp, Kp = packed_shape(F, H, k)
+    shape = (round_up(Kp, 64), Fp)
+    if out is None:
+        out = torch.zeros(shape, dtype=weight.dtype, device=weight.device)
+    elif out.shape != shape or out.dtype != weight.dtype or out.device != weight.device or not out.is_contiguous():
+        raise ValueError("pack_conv_weight_t: out must be a contiguous [round_up(Kp, 64), Fp] buffer like the weight")
+    with torch.no_grad():
+        out[: k * H, :F].unflatten(0, (k, H)).copy_(weight.detach().permute(2, 1, 0))
+    return out
+
+
+def _packed_weight_t(model) -> torch.Tensor:
+    """The model's persistent ``WpT`` buffer, refilled on every call like ``Wp``."""
+    w = model.conv.weight
+    F, H, k = w.shape
+    Fp, Kp = packed_shape(F, H, k)
+    buf = getattr(model, "_mpit_wpt", None)
+    if buf is None or buf.device != w.device or buf.shape != (round_up(Kp, 64), Fp) or buf.dtype != w.dtype:
+        buf = None
+    buf = pack_conv_weight_t(w, buf)
+    model._mpit_wpt = buf
+    return buf
+
+
+def stack_sentences(q: torch.Tensor, a_pos: torch.Tensor, a_neg: torch.Tensor, pad_idx: int) -> torch.Tensor:
+    """``[q; a_pos; a_neg]`` as one ``[3n, T]`` int64 batch, padded with ``pad_idx`` to the longest."""
+    n = q.shape[0]
+    if q.dim() != 2 or a_pos.dim() != 2 or a_neg.dim() != 2 or a_pos.shape[0] != n or a_neg.shape[0] != n:
+        raise ValueError("per_example_grads: q [n, Tq], a_pos [n, Tp], a_neg [n, Tn]")
+    T = max(q.shape[1], a_pos.shape[1], a_neg.shape[1])
+    tok = torch.full((3 * n, T), int(pad_idx), dtype=torch.int64, device=q.device)
+    for i, t in enumerate((q, a_pos, a_neg)):
+        tok[i * n: (i + 1) * n, : t.shape[1]] = t
+    return tok
+
+
+def per_example_grads(model, flat, q: torch.Tensor, a_pos: torch.Tensor, a_neg: torch.Tensor, margin: float,
+                      out: Optional[torch.Tensor] = None, parts: Optional[dict] = None):
+    """``models.bicnn.per_example_grads`` on the fused kernels, forward and backward: returns
+    ``(g, err)``, ``g`` ``[n, flat.numel]`` fp32 with row ``k`` the gradient of example ``k``'s margin
+    loss alone (laid out like ``flat``: the parameters at ``flat.offsets``, zeros in the alignment gaps
+    and in the embedding rows the example does not touch) and ``err`` ``[n]`` the per-example hinge
+    values. No autograd inside (grad mode does not matter); the forward half is :func:`encode`'s and
+    :func:`gesd_gather`'s bits. ``out``: a contiguous ``[n, flat.numel]`` buffer to use for ``g`` (it is
+    zeroed first); ``parts``: a dict that receives the intermediates (tok, win, c, y, arg, den, sc, gy,
+    dm, dc, dwin, da, de)."""
+    from . import conv as C
+
+    conv = model.conv
+    F, H, k = conv.weight.shape
+    if conv.stride != (1,) or conv.padding != (0,) or conv.dilation != (1,) or conv.groups != 1:
+        raise ValueError("seq.per_example_grads: a plain stride-1 Conv1d is expected")
+    E, Wh, bh, bc = model.embed.weight.detach(), model.hidden.weight.detach(), model.hidden.bias, conv.bias
+    bh = bh.detach() if bh is not None else None
+    bc = bc.detach() if bc is not None else None
+    V, D = E.shape
+    offs = {id(p): o for p, o in zip(flat.params, flat.offsets)}
+    try:
+        offE, offWh, offW = (offs[id(p)] for p in (model.embed.weight, model.hidden.weight, conv.weight))
+        offBh = offs[id(model.hidden.bias)] if bh is not None else -1
+        offB = offs[id(conv.bias)] if bc is not None else -1
+    except KeyError:
+        raise ValueError("seq.per_example_grads: flat does not hold the model's parameters") from None
+    f32, dev = torch.float32, q.device
+    with torch.no_grad():
+        tok = stack_sentences(q, a_pos, a_neg, model.pad_idx)
+        S, T = tok.shape
+        n = S // 3
+        if n == 0 or T == 0:
+            raise ValueError("seq.per_example_grads: needs at least one example and one token")
+        if out is None:
+            g = torch.zeros((n, flat.numel), dtype=f32, device=dev)
+        else:
+            if out.shape != (n, flat.numel):
+                raise ValueError("seq.per_example_grads: out [n, flat.numel]")
+            g = out.zero_()
+        _check("per_example_grads", dev, tok=(tok, torch.int64), E=(E, f32), Wh=(Wh, f32), bh=(bh, f32), bc=(bc, f32),
+               out=(g, f32))
+        m, st, di = native(), _stream(tok), dev.index
+        # forward: encode()'s kernels, the arg-max and the clamped norm kept
+        wp = _packed_weight(model)
+        Fp, Kp = wp.shape
+        win = hidden_windows(tok, E, Wh, bh, k, Kp)
+        c = C.gemm_nt(win, wp)  # [S*T, Fp]
+        y = torch.empty((S, F), dtype=f32, device=dev)
+        arg = torch.empty((S, F), dtype=torch.int32, device=dev)
+        den = torch.empty((S,), dtype=f32, device=dev)
+        m.seq_max_norm_arg(di, st, c.data_ptr(), Fp, tok.data_ptr(), S, T, k, int(model.pad_idx), _ptr(bc), F,
+                           float(model.norm.eps), y.data_ptr(), arg.data_ptr(), den.data_ptr())
+        # scores, hinge and the gradient of the three encodings
+        err = torch.empty((n,), dtype=f32, device=dev)
+        sc = torch.empty((2, n), dtype=f32, device=dev)
+        gy = torch.empty((S, F), dtype=f32, device=dev)
+        m.gesd_pair_bwd(di, st, y.data_ptr(), n, F, float(margin), err.data_ptr(), sc.data_ptr(), gy.data_ptr())
+        # through the normalisation, the ReLU and the max: one non-zero per (sentence, filter)
+        dm = torch.empty((S, F), dtype=f32, device=dev)
+        dc = torch.empty((S * T, Fp), dtype=f32, device=dev)
+        m.seq_norm_max_bwd(di, st, gy.data_ptr(), y.data_ptr(), arg.data_ptr(), den.data_ptr(), S, T, F, Fp,
+                           float(model.norm.eps), dm.data_ptr(), dc.data_ptr())
+        dwin = C.gemm_nt(dc, _packed_weight_t(model))  # [S*T, round_up(Kp, 64)]
+        m.seq_conv_wgrad_pe(di, st, dm.data_ptr(), arg.data_ptr(), win.data_ptr(), n, T, F, H, k, Kp, g.data_ptr(),
+                            g.stride(0), offW, offB)
+        da = torch.empty((S * T, H), dtype=f32, device=dev)
+        de = torch.empty((S * T, D), dtype=f32, device=dev)
+        m.seq_hidden_bwd(di, st, dwin.data_ptr(), dwin.shape[1], win.data_ptr(), Kp, S, T, H, k, Wh.data_ptr(), D,
+                         da.data_ptr(), de.data_ptr())
+        m.seq_hidden_embed_grad_pe(di, st, da.data_ptr(), de.data_ptr(), tok.data_ptr(), E.data_ptr(), V, n, T, H, D,
+                                   int(model.pad_idx), g.data_ptr(), g.stride(0), offE, offWh, offBh)
+    if parts is not None:
+        parts.update(tok=tok, win=win, c=c, y=y, arg=arg, den=den, sc=sc, gy=gy, dm=dm, dc=dc, dwin=dwin, da=da, de=de)
+    COUNTERS["pegrad_fused"] += 1
+    return g, err
