@@ -553,6 +553,22 @@ PYBIND11_MODULE(_mpit, m) {
            [](Window& w, int m, int64_t off, uintptr_t src, bool src_dev, int64_t nelem, bool bf16, float a, float b,
               uintptr_t s) { w.accumulate(m, off, src, src_dev, nelem, bf16, a, b, S(s)); },
            py::call_guard<py::gil_scoped_release>())
+      .def("put_plan",
+           [](Window& w, int m, int64_t off, std::vector<std::array<int64_t, 2>> loops, uintptr_t table, int64_t R,
+              int64_t L, int64_t per, int unit, int64_t lo, int64_t hi, uintptr_t packed, uintptr_t s) {
+             w.put_plan(m, off, CopyPlan{std::move(loops), table, R, L, per, unit, lo, hi}, packed, S(s));
+           },
+           py::arg("member"), py::arg("off"), py::arg("loops"), py::arg("table"), py::arg("R"), py::arg("L"),
+           py::arg("per"), py::arg("unit"), py::arg("lo"), py::arg("hi"), py::arg("packed"), py::arg("stream"),
+           py::call_guard<py::gil_scoped_release>())
+      .def("get_plan",
+           [](Window& w, int m, int64_t off, std::vector<std::array<int64_t, 2>> loops, uintptr_t table, int64_t R,
+              int64_t L, int64_t per, int unit, int64_t lo, int64_t hi, uintptr_t packed, uintptr_t s) {
+             w.get_plan(m, off, CopyPlan{std::move(loops), table, R, L, per, unit, lo, hi}, packed, S(s));
+           },
+           py::arg("member"), py::arg("off"), py::arg("loops"), py::arg("table"), py::arg("R"), py::arg("L"),
+           py::arg("per"), py::arg("unit"), py::arg("lo"), py::arg("hi"), py::arg("packed"), py::arg("stream"),
+           py::call_guard<py::gil_scoped_release>())
       .def("lock", &Window::lock, py::call_guard<py::gil_scoped_release>())
       .def("try_lock", &Window::try_lock)
       .def("unlock", &Window::unlock)
@@ -574,6 +590,15 @@ PYBIND11_MODULE(_mpit, m) {
       py::arg("dev"), py::arg("stream"), py::arg("op"), py::arg("dtype"), py::arg("srcs"), py::arg("dsts"),
       py::arg("n"), py::call_guard<py::gil_scoped_release>());
   m.def("ar_oneshot_bytes", &Window::oneshot_bytes);
+  m.def(
+      "type_copy",
+      [](int dev, uintptr_t s, int dir, uintptr_t strided, uintptr_t packed, std::vector<std::array<int64_t, 2>> loops,
+         uintptr_t table, int64_t R, int64_t L, int64_t per, int unit, int max_blocks, bool wide) {
+        type_copy(dev, S(s), dir, strided, packed, loops, table, R, L, per, unit, max_blocks, wide);
+      },
+      py::arg("dev"), py::arg("stream"), py::arg("dir"), py::arg("strided"), py::arg("packed"), py::arg("loops"),
+      py::arg("table"), py::arg("R"), py::arg("L"), py::arg("per"), py::arg("unit"), py::arg("max_blocks") = 0,
+      py::arg("wide") = false, py::call_guard<py::gil_scoped_release>());
 
   py::class_<ServerRule>(m, "ServerRule")
       .def(py::init<>())

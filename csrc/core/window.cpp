@@ -195,6 +195,30 @@ void Window::get(uintptr_t dst, int m, int64_t off, int64_t n, hipStream_t s) {
   }
 }
 
+void Window::copy_plan(int dir, int m, int64_t off, const CopyPlan& p, uintptr_t packed, hipStream_t s) {
+  const Remote& r = remote_.at(size_t(m));
+  const char* what = dir ? "mpit: Put outside the target window" : "mpit: Get outside the target window";
+  if (p.lo > p.hi) throw std::invalid_argument("mpit: one-sided plan with lo > hi");
+  if (p.hi == p.lo) return;  // nothing to move
+  if (off < 0 || off + p.lo < 0 || off + p.hi > r.bytes) throw std::out_of_range(what);
+  if (!r.ptr) throw std::runtime_error("mpit: target window not mapped on this rank");
+  const uintptr_t strided = reinterpret_cast<uintptr_t>(r.ptr) + uintptr_t(off);
+  if (r.device) {
+    if (eng_.device() < 0) throw std::runtime_error("mpit: device target window on a rank without a device");
+    type_copy(eng_.device(), s, dir, strided, packed, p.loops, p.table, p.R, p.L, p.per, p.unit);
+  } else {
+    type_copy(-1, nullptr, dir, strided, packed, p.loops, p.table, p.R, p.L, p.per, p.unit);
+  }
+}
+
+void Window::put_plan(int m, int64_t off, const CopyPlan& p, uintptr_t packed, hipStream_t s) {
+  copy_plan(1, m, off, p, packed, s);
+}
+
+void Window::get_plan(int m, int64_t off, const CopyPlan& p, uintptr_t packed, hipStream_t s) {
+  copy_plan(0, m, off, p, packed, s);
+}
+
 void Window::accumulate(int m, int64_t off, uintptr_t src, bool src_dev, int64_t nelem, bool bf16, float a, float b,
                         hipStream_t s) {
   const Remote& r = remote_.at(size_t(m));

@@ -14,6 +14,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <atomic>
 #include <cstdint>
 #include <string>
@@ -27,6 +28,16 @@ struct alignas(64) WinCtl {
   std::atomic<int64_t> lock;  // 0 free, >0 shared holders, -1 exclusive
   std::atomic<int64_t> epoch;
   char pad[48];
+};
+
+// A derived-datatype layout relative to a byte offset in a window (kernels.h type_copy: loops,
+// run table, unit) and the bytes it touches, [lo, hi) relative to that offset.
+struct CopyPlan {
+  std::vector<std::array<int64_t, 2>> loops;
+  uintptr_t table;  // on this rank's device for a device target, host memory for a host target
+  int64_t R, L, per;
+  int unit;
+  int64_t lo, hi;
 };
 
 class Window {
@@ -56,6 +67,13 @@ class Window {
   // data movement (member index; offsets in bytes). src/dst device-ness given by caller.
   void put(int m, int64_t off, uintptr_t src, int64_t n, hipStream_t s);
   void get(uintptr_t dst, int m, int64_t off, int64_t n, hipStream_t s);
+  // Put / Get with a derived target datatype in one type_copy launch: the layout `p` at byte
+  // offset `off` of member m's window is the strided side (the peer-mapped pointer for a device
+  // window, launched on s; the host twin for a host window), `packed` the local contiguous
+  // stream (device memory for a device target, host memory for a host target). The plan's span
+  // is checked against the target window (std::out_of_range, like put). Complete after flush(s).
+  void put_plan(int m, int64_t off, const CopyPlan& p, uintptr_t packed, hipStream_t s);
+  void get_plan(int m, int64_t off, const CopyPlan& p, uintptr_t packed, hipStream_t s);
   // dst[m][off..] = a*src + b*dst (fp32|bf16 elements), atomic w.r.t. other accumulates
   // through the exclusive lock of the target.
   void accumulate(int m, int64_t off, uintptr_t src, bool src_dev, int64_t nelem, bool bf16, float a, float b,
@@ -104,6 +122,7 @@ class Window {
   };
   std::vector<Remote> remote_;
   std::vector<int> held_;  // lock mode held per member: 0 none, 1 shared, 2 exclusive
+  void copy_plan(int dir, int m, int64_t off, const CopyPlan& p, uintptr_t packed, hipStream_t s);
   void* ar_tmp_ = nullptr;  // one-shot in place: the private result, copied back after B2
   int64_t ar_tmp_bytes_ = 0;
 };

@@ -360,4 +360,20 @@ int peer_dtype_size(int dtype);
 void peer_reduce(int dev, hipStream_t s, int op, int dtype, const std::vector<uintptr_t>& srcs,
                  const std::vector<uintptr_t>& dsts, int64_t n);
 
+// ---- derived-datatype pack / unpack (type_copy.hip) ------------------------------------
+// dir 0: gather the strided layout at `strided` into the contiguous stream at `packed`; dir 1:
+// scatter the stream into the layout. The layout is up to three `loops` (count, byte stride),
+// outermost first, around R runs: table = int64 [offs[R] | prefix[R + 1]] (device memory, host
+// when dev < 0), L = the common run length or 0, per = prefix[R] = the packed bytes of one
+// innermost iteration (R * L when L != 0). table == 0 with R == 1, L != 0: one run at offset 0.
+// Packed order: loops outermost to innermost, runs in table order, ascending bytes. unit (a power
+// of two <= 16) divides every offset, length, stride (of a loop with count > 1) and both
+// addresses: bytes moved per lane and access. max_blocks > 0 lowers the grid cap; wide forces the
+// 64-bit index arithmetic that a packed stream of 4 GiB or more selects by itself. The layout is
+// trusted: the caller has checked its span against the buffers. Allocates and synchronises
+// nothing. Overlapping runs in a scatter leave one writer's bytes.
+void type_copy(int dev, hipStream_t s, int dir, uintptr_t strided, uintptr_t packed,
+               const std::vector<std::array<int64_t, 2>>& loops, uintptr_t table, int64_t R, int64_t L, int64_t per,
+               int unit, int max_blocks = 0, bool wide = false);
+
 }  // namespace mpit

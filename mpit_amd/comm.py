@@ -23,6 +23,7 @@ from typing import Callable, List, Optional, Sequence
 
 import torch
 
+from . import datatypes as _dt
 from . import runtime as _rt
 from ._ext import native
 
@@ -523,6 +524,8 @@ class Comm:
         if datatype is not None and not datatype.is_contiguous_basic():
             buf = datatype.pack(buf, count)
             count = None
+        elif isinstance(buf, torch.Tensor) and not buf.is_contiguous():
+            buf = _dt.pack_tensor(buf)  # a strided view: its elements in logical order, one launch
         t = _flat(buf, count)
         if t.is_cuda:  # the receiver pulls the bytes: what the stream is still producing must land first
             torch.cuda.current_stream(t.device).synchronize()
@@ -539,6 +542,17 @@ class Comm:
             rid = _rt.engine().irecv(stage.data_ptr(), _nbytes(stage), stage.is_cuda, self._to_world(source), int(tag), ctx)
             return Request(self, rid, keep=(stage, buf), itemsize=datatype.Get_size(),
                            on_done=lambda: datatype.unpack(stage, buf, count))
+        if isinstance(buf, torch.Tensor) and not buf.is_contiguous():
+            # a strided view: receive into a contiguous staging buffer that starts as the view's own
+            # elements (a shorter message leaves the rest as it was) and scatter it on completion
+            _dt.check_writable_layout(buf)
+            stage = _dt.pack_tensor(buf)
+            t = _flat(stage, count)
+            if t.is_cuda:  # the sender's copy into the staging buffer must not overtake that fill
+                torch.cuda.current_stream(t.device).synchronize()
+            rid = _rt.engine().irecv(t.data_ptr(), _nbytes(t), t.is_cuda, self._to_world(source), int(tag), ctx)
+            return Request(self, rid, keep=(stage, buf), itemsize=t.element_size(),
+                           on_done=lambda: _dt.unpack_tensor(stage, buf))
         t = _flat(buf, count)
         rid = _rt.engine().irecv(t.data_ptr(), _nbytes(t), t.is_cuda, self._to_world(source), int(tag), ctx)
         return Request(self, rid, keep=(t,), itemsize=t.element_size())

@@ -3,14 +3,26 @@ type constructors (mpifuncs.c Type_* / Pack* wrappers, SURVEY Appendix A "Dataty
 
 A :class:`Datatype` is a *typemap*: a list of (byte displacement, basic type) plus lower
 bound and extent. ``pack`` / ``unpack`` move ``count`` instances between a tensor (viewed
-as bytes) and a contiguous byte stream with one gather / scatter index op, so they work
-unchanged on host tensors and on HBM tensors (the index tensor is cached per type).
+as bytes) and a contiguous byte stream in one launch of the type_copy kernel
+(csrc/kernels/type_copy.hip; its host twin for host tensors) driven by a compact layout
+:class:`Plan` (loops around a run table, built once per type). The byte-index gather /
+scatter remains as the fallback: ``MPIT_DTYPE_KERNEL=0``, a negative displacement, or a
+native module that does not load. Either way the layout's last byte is checked against the
+buffer on the host first (``IndexError``). ``layout_of`` gives the same kind of plan for a
+non-contiguous tensor, which lets point-to-point calls send and receive strided views.
 """
 from __future__ import annotations
 
+import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
+
+# which path moved the bytes: `kernel` = type_copy launches (pack / unpack / send / recv and
+# the packing of a derived one-sided origin), `index` = the byte-index fallback, `rma_kernel` =
+# one-launch Put / Get on a derived target type, `rma_copies` = per-run peer copies
+COUNTERS = {"kernel": 0, "index": 0, "rma_kernel": 0, "rma_copies": 0}
 
 _BASIC: Dict[str, Tuple[int, Optional[torch.dtype]]] = {
     "CHAR": (1, torch.int8), "BYTE": (1, torch.uint8), "SHORT": (2, torch.int16), "INT": (4, torch.int32),
@@ -21,6 +33,207 @@ _BASIC: Dict[str, Tuple[int, Optional[torch.dtype]]] = {
     "2INT": (8, None), "LONG_DOUBLE_INT": (32, None), "PACKED": (1, torch.uint8), "UB": (0, None), "LB": (0, None),
     "BFLOAT16": (2, torch.bfloat16), "HALF": (2, torch.float16), "BOOL": (1, torch.bool),
 }
+
+
+# -------------------------------------------------------------------- layout plans
+
+def _low_bit(x: int) -> int:
+    """The largest power of two <= 16 that divides x (16 for 0)."""
+    x = int(x) & 15
+    return (x & -x) if x else 16
+
+
+def _fold_once(offs: np.ndarray, lens: np.ndarray):
+    """offs / lens of R runs -> ((n, stride), offs[:p], lens[:p]) for the smallest period p < R
+    with lens[i + p] == lens[i] and offs[i + p] == offs[i] + stride, or None. One vectorised
+    comparison per divisor of R."""
+    R = len(offs)
+    small = [p for p in range(1, int(R ** 0.5) + 1) if R % p == 0]
+    for p in sorted(set(small + [R // p for p in small])):
+        if p == R or lens[p] != lens[0]:
+            continue
+        d = int(offs[p] - offs[0])
+        if np.array_equal(lens[p:], lens[:-p]) and bool((offs[p:] - offs[:-p] == d).all()):
+            return (R // p, d), offs[:p], lens[:p]
+    return None
+
+
+class Plan:
+    """`loops` around a run table, the layout type_copy (csrc/kernels/type_copy.hip) walks.
+
+    loops: up to three (n, stride bytes) with n > 1, outermost first; offs / lens: the R runs
+    (byte offset, length > 0) in packed order; prefix: the R + 1 prefix sums of lens; L: the
+    common run length or 0; per = prefix[R]; total: the packed bytes; [lo, hi): the bytes
+    touched relative to the base address (hi == lo == 0 for an empty plan); align: the largest
+    power of two <= 16 dividing every offset, length and stride. Packed order: loops outermost
+    to innermost, runs in table order, ascending bytes."""
+
+    def __init__(self, loops, offs: np.ndarray, lens: np.ndarray, tables: Optional[dict] = None):
+        self.loops = tuple((int(n), int(s)) for n, s in loops)
+        if len(self.loops) > 3:
+            raise ValueError("a layout plan holds at most three loops")
+        self.offs, self.lens = offs, lens
+        self.R = len(offs)
+        self.prefix = np.zeros(self.R + 1, dtype=np.int64)
+        np.cumsum(lens, out=self.prefix[1:])
+        self.per = int(self.prefix[-1])
+        iters = 1
+        for n, _ in self.loops:
+            iters *= n
+        self.total = iters * self.per
+        if self.total == 0:
+            self.L = self.lo = self.hi = 0
+            self.align = 16
+        else:
+            self.L = int(lens[0]) if bool((lens == lens[0]).all()) else 0
+            self.lo, self.hi = int(offs.min()), int((offs + lens).max())
+            bits = int(np.bitwise_or.reduce(offs | lens))
+            for n, s in self.loops:
+                self.lo += min(0, (n - 1) * s)
+                self.hi += max(0, (n - 1) * s)
+                bits |= s
+            self.align = _low_bit(bits)
+        self._tables = tables if tables is not None else {}  # device -> uploaded [offs | prefix]
+        self._off0 = int(offs[0]) if self.R == 1 else 0
+        self._loops = [list(x) for x in self.loops]  # as the binding takes them
+
+    def unit(self, strided_addr: int, packed_addr: int) -> int:
+        """Bytes a lane moves per access between these two base addresses."""
+        bits = self.align | strided_addr | packed_addr  # align <= 16 bounds the lowest set bit
+        return bits & -bits
+
+    def table(self, device) -> Tuple[int, int, Optional[torch.Tensor]]:
+        """(table address, byte offset to add to the strided base, the tensor to keep alive). One
+        run needs no table: its offset moves into the base. Otherwise int64 [offs | prefix],
+        uploaded once per device with a host-blocking copy (complete on return, so any stream
+        may read it) and cached."""
+        if self.R == 1:
+            return 0, self._off0, None
+        t = self._tables.get(device)
+        if t is None:
+            t = torch.from_numpy(np.concatenate([self.offs, self.prefix])).to(device, non_blocking=False)
+            self._tables[device] = t
+        return t.data_ptr(), 0, t
+
+    def self_overlap(self) -> bool:
+        """True when a one-run plan's loops may write a byte twice (a zero or overlapping stride)."""
+        span = self.L
+        for n, s in sorted(self.loops, key=lambda ns: abs(ns[1])):
+            if abs(s) < span:
+                return True
+            span += (n - 1) * abs(s)
+        return False
+
+    def __repr__(self):
+        return f"Plan(loops={self.loops}, R={self.R}, L={self.L}, total={self.total}, span=[{self.lo}, {self.hi}))"
+
+
+_native_ok: Optional[bool] = None
+
+
+def kernel_enabled() -> bool:
+    """type_copy moves the bytes unless MPIT_DTYPE_KERNEL=0 or the native module does not load."""
+    global _native_ok
+    if os.environ.get("MPIT_DTYPE_KERNEL", "1") == "0":
+        return False
+    if _native_ok is None:
+        try:
+            from ._ext import native
+
+            native()
+            _native_ok = True
+        except Exception:
+            _native_ok = False
+    return _native_ok
+
+
+_nat = None
+
+
+def run_plan(plan: Plan, direction: int, strided: torch.Tensor, packed: torch.Tensor, max_blocks: int = 0,
+             wide: bool = False):
+    """One type_copy launch (the host twin for CPU tensors): direction 0 gathers the plan's bytes
+    at `strided`'s first byte into `packed`, 1 scatters. The caller has checked the plan's span
+    against the strided buffer and that `packed` is contiguous, on the same device and holds
+    plan.total bytes. Kept short: at small sizes a call costs what this function costs."""
+    global _nat
+    if plan.total == 0:
+        return
+    if _nat is None:
+        from ._ext import native
+
+        _nat = native()
+    dev, stream = -1, 0
+    if strided.is_cuda:
+        dev = strided.device.index
+        stream = torch._C._cuda_getCurrentRawStream(dev)
+    tab, off, _keep = plan.table(strided.device)
+    sp, pp = strided.data_ptr() + off, packed.data_ptr()
+    bits = plan.align | sp | pp
+    _nat.type_copy(dev, stream, direction, sp, pp, plan._loops, tab, plan.R, plan.L, plan.per, bits & -bits,
+                   max_blocks, wide)
+    COUNTERS["kernel"] += 1
+
+
+def layout_of(t: torch.Tensor) -> Plan:
+    """The plan of a strided tensor's bytes in logical (row-major) order, relative to its
+    data_ptr(): size-1 dims dropped, adjacent dims merged where the outer stride continues the
+    inner one, a unit-stride innermost dim turned into the run. ValueError when more than three
+    loops remain or an offset is negative."""
+    es = t.element_size()
+    dims = [(int(n), int(s) * es) for n, s in zip(t.shape, t.stride()) if n != 1]
+    if any(n == 0 for n, _ in dims):
+        return Plan((), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64))
+    if any(s < 0 for _, s in dims):
+        raise ValueError("layout_of: negative strides (negative offsets) are not supported")
+    merged: List[Tuple[int, int]] = []
+    for n, s in dims:
+        if merged and merged[-1][1] == n * s:
+            merged[-1] = (merged[-1][0] * n, s)
+        else:
+            merged.append((n, s))
+    run = es
+    if merged and merged[-1][1] == es:
+        run = merged.pop()[0] * es
+    if len(merged) > 3:
+        raise ValueError(f"layout_of: {len(merged)} strided loops remain after collapsing; more than three loops "
+                         "are not supported (make the tensor contiguous first)")
+    return Plan(merged, np.zeros(1, dtype=np.int64), np.array([run], dtype=np.int64))
+
+
+def pack_tensor(t: torch.Tensor) -> torch.Tensor:
+    """A non-contiguous tensor's elements in logical order as a new contiguous 1-D tensor."""
+    out = torch.empty(t.numel(), dtype=t.dtype, device=t.device)
+    if kernel_enabled():
+        run_plan(layout_of(t), 0, _bytes_at(t), out.view(torch.uint8))
+    else:
+        COUNTERS["index"] += 1
+        out.copy_(t.reshape(-1))
+    return out
+
+
+def unpack_tensor(packed: torch.Tensor, t: torch.Tensor):
+    """Scatter a contiguous stream of t.numel() elements into the non-contiguous tensor `t`."""
+    check_writable_layout(t)
+    if packed.numel() != t.numel() or packed.dtype != t.dtype or packed.device != t.device:
+        raise ValueError("unpack_tensor: the stream must hold t.numel() elements of t's dtype on t's device")
+    if kernel_enabled():
+        run_plan(layout_of(t), 1, _bytes_at(t), packed.contiguous().reshape(-1).view(torch.uint8))
+    else:
+        COUNTERS["index"] += 1
+        t.copy_(packed.reshape(-1).view(t.dtype).reshape(t.shape))
+    return t
+
+
+def check_writable_layout(t: torch.Tensor):
+    if layout_of(t).self_overlap():
+        raise ValueError("cannot receive / unpack into a tensor with a zero or overlapping stride")
+
+
+def _bytes_at(t: torch.Tensor) -> torch.Tensor:
+    """A one-element uint8 tensor at t's first byte (the base address of its layout, kept alive by
+    the storage it shares)."""
+    return torch.as_strided(t, (1,), (1,)).view(torch.uint8)[:1] if t.numel() else t.reshape(-1).view(torch.uint8)
 
 
 class Datatype:
@@ -34,6 +247,9 @@ class Datatype:
         self.committed = committed
         self._attrs = {}
         self._idx_cache = {}
+        self._fold_cache = None  # the folded instance layout (plan)
+        self._plan_cache = {}  # count -> Plan
+        self._tab_cache = {}  # device -> uploaded run table, shared by the plans of every count
 
     # ---------------------------------------------------------------- queries
     def Get_size(self) -> int:
@@ -68,6 +284,8 @@ class Datatype:
 
     def Free(self):
         self._idx_cache.clear()
+        self._plan_cache.clear()
+        self._tab_cache.clear()
 
     def Dup(self) -> "Datatype":
         return Datatype(list(self.typemap), self.lb, self.extent, self._name, ("DUP", (), (self,)))
@@ -111,11 +329,80 @@ class Datatype:
         nbytes = buf.numel() * buf.element_size()
         return max(0, (nbytes - self.Get_true_extent()[1]) // max(1, self.extent) + 1) if self.extent else 1
 
-    def pack(self, buf: torch.Tensor, count: Optional[int] = None) -> torch.Tensor:
-        """Gather `count` instances from `buf` into a contiguous uint8 tensor."""
-        count = self._count_for(buf, count)
-        raw = buf.contiguous().reshape(-1).view(torch.uint8)
-        return raw[self._byte_index(count, raw.device)]
+    # ---------------------------------------------------------------- layout plan
+    def _folded(self):
+        """(inner loops, offs, lens) of ONE instance: the merged runs of the type map, an
+        arithmetic progression of equal-length runs folded into a loop (at most twice)."""
+        if self._fold_cache is None:
+            tm = [(d, _BASIC[b][0]) for d, b in self.typemap if _BASIC[b][0]]
+            arr = np.array(tm, dtype=np.int64).reshape(-1, 2)
+            offs, lens = arr[:, 0], arr[:, 1]
+            if len(offs) > 1:  # merge adjacent entries, as runs() does
+                first = np.concatenate([[True], offs[1:] != offs[:-1] + lens[:-1]])
+                starts = np.flatnonzero(first)
+                lens = np.add.reduceat(lens, starts)
+                offs = offs[starts]
+            loops = []
+            while len(loops) < 2:
+                f = _fold_once(offs, lens)
+                if f is None:
+                    break
+                loops.append(f[0])
+                offs, lens = f[1], f[2]
+            self._fold_cache = (loops, np.ascontiguousarray(offs), np.ascontiguousarray(lens))
+        return self._fold_cache
+
+    def plan(self, count: int) -> Plan:
+        """The layout of `count` instances (see :class:`Plan`): the folded instance under the
+        loop (count, extent). Built once per type; a count costs nothing but the small object."""
+        count = int(count)
+        p = self._plan_cache.get(count)
+        if p is None:
+            loops, offs, lens = self._folded()
+            loops = list(loops)
+            if count <= 0 or not len(offs):
+                p = Plan((), offs[:0], lens[:0])
+            else:
+                if count > 1:
+                    if loops and loops[0][0] * loops[0][1] == self.extent:  # instances continue the outer loop
+                        loops[0] = (loops[0][0] * count, loops[0][1])
+                    elif not loops and len(offs) == 1 and int(lens[0]) == self.extent:  # contiguous instances
+                        lens = lens * count
+                    else:
+                        loops.insert(0, (count, self.extent))
+                tables = self._tab_cache if len(lens) > 1 else None
+                p = Plan(loops, offs, lens, tables)
+            self._plan_cache[count] = p
+        return p
+
+    def _check_span(self, plan: Plan, nbytes: int):
+        """Host-side guard of both paths: the plan's bytes lie inside the buffer (a negative
+        displacement may reach back at most the buffer's length: the index path wraps it)."""
+        if plan.total and (plan.hi > nbytes or plan.lo < -nbytes):
+            raise IndexError(f"{self!r}: bytes [{plan.lo}, {plan.hi}) of the layout lie outside a buffer of {nbytes} bytes")
+
+    def pack(self, buf: torch.Tensor, count: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Gather `count` instances from `buf` into a contiguous uint8 tensor (`out`, when given:
+        uint8, contiguous, on buf's device, exactly the packed size)."""
+        if count is None:
+            count = self._count_for(buf, None)
+        plan = self._plan_cache.get(count) or self.plan(count)
+        raw = buf if buf.is_contiguous() else buf.contiguous()
+        nbytes = raw.numel() * raw.element_size()
+        if plan.hi > nbytes or plan.lo < -nbytes:
+            self._check_span(plan, nbytes)
+        if out is not None and (out.dtype != torch.uint8 or out.numel() != plan.total or out.device != raw.device
+                                or not out.is_contiguous()):
+            raise ValueError("pack: `out` must be uint8, contiguous, on the buffer's device and of the packed size")
+        if plan.lo < 0 or not kernel_enabled():
+            COUNTERS["index"] += 1
+            raw = raw.reshape(-1).view(torch.uint8)
+            data = raw[self._byte_index(count, raw.device)]
+            return data if out is None else out.copy_(data)
+        if out is None:
+            out = torch.empty(plan.total, dtype=torch.uint8, device=raw.device)
+        run_plan(plan, 0, raw, out)
+        return out
 
     def staging(self, buf: torch.Tensor, count: Optional[int] = None) -> torch.Tensor:
         count = self._count_for(buf, count)
@@ -123,11 +410,28 @@ class Datatype:
 
     def unpack(self, packed: torch.Tensor, buf: torch.Tensor, count: Optional[int] = None):
         """Scatter a packed byte stream into `buf` (in place)."""
-        count = self._count_for(buf, count)
+        if count is None:
+            count = self._count_for(buf, None)
         if not buf.is_contiguous():
             raise ValueError("unpack target must be contiguous")
-        raw = buf.reshape(-1).view(torch.uint8)
-        raw[self._byte_index(count, raw.device)] = packed.reshape(-1)[: count * self.Get_size()].to(raw.device)
+        plan = self._plan_cache.get(count) or self.plan(count)
+        nbytes = buf.numel() * buf.element_size()
+        if plan.hi > nbytes or plan.lo < -nbytes:
+            self._check_span(plan, nbytes)
+        if plan.lo < 0 or not kernel_enabled():
+            COUNTERS["index"] += 1
+            raw = buf.reshape(-1).view(torch.uint8)
+            raw[self._byte_index(count, raw.device)] = packed.reshape(-1)[: count * self.Get_size()].to(raw.device)
+            return buf
+        src = packed
+        if src.dtype != torch.uint8 or src.dim() != 1 or src.device != buf.device or not src.is_contiguous():
+            src = packed.reshape(-1)
+            if src.dtype != torch.uint8:
+                src = src.contiguous().view(torch.uint8)
+            src = src.to(buf.device).contiguous()
+        if src.numel() < plan.total:
+            raise ValueError(f"unpack: the packed stream holds {src.numel()} bytes, {count} x {self!r} needs {plan.total}")
+        run_plan(plan, 1, buf, src)
         return buf
 
     def runs(self, count: int) -> List[Tuple[int, int]]:
@@ -372,8 +676,12 @@ def Type_match_size(typeclass: int, size: int) -> Datatype:
 def Pack(inbuf: torch.Tensor, incount: int, datatype: Datatype, outbuf: torch.Tensor, position: int) -> int:
     """Append `incount` instances to the byte buffer `outbuf` at `position`; returns the
     new position (MPI_Pack)."""
-    data = datatype.pack(inbuf, incount)
     out = outbuf.reshape(-1).view(torch.uint8)
+    n = int(incount) * datatype.Get_size()
+    if outbuf.is_contiguous() and out.device == inbuf.device and 0 <= position and position + n <= out.numel():
+        datatype.pack(inbuf, incount, out=out[position: position + n])  # straight into place
+        return position + n
+    data = datatype.pack(inbuf, incount)
     out[position: position + data.numel()] = data.to(out.device)
     return position + data.numel()
 

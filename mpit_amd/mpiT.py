@@ -454,13 +454,42 @@ def _target_runs(win, target_disp, target_count, target_type, nbytes):
     return [(base + o, n) for o, n in runs]
 
 
+def _target_plan(target_count, target_type, nbytes):
+    """The layout plan of a derived target (count, datatype) when the type_copy path serves it,
+    else None (basic type, MPIT_DTYPE_KERNEL=0, negative displacement: per-run copies)."""
+    if target_type is None or target_type.is_contiguous_basic() or not _dt.kernel_enabled():
+        return None
+    plan = target_type.plan(target_count)
+    if plan.lo < 0:
+        return None
+    if plan.total != nbytes:  # the same refusal as _target_runs
+        raise ValueError(f"one-sided: origin carries {nbytes} bytes, target (count {target_count}, {target_type}) "
+                         f"{plan.total}")
+    return plan
+
+
+def _window_side(win, target_rank, like: torch.Tensor) -> torch.device:
+    """The device a packed stream must live on to be moved by one launch against that target."""
+    if win._w.remote_device(target_rank):
+        return like.device if like.is_cuda else _rt.device()
+    return torch.device("cpu")
+
+
 def Put(origin, origin_count, origin_type, target_rank, target_disp, target_count, target_type, win):
     """MPI_Put (mpifuncs.c:1656): origin (count, datatype) packed, scattered over the target
-    datatype's runs in the target window (one peer copy per contiguous run)."""
+    datatype's layout in the target window: one type_copy launch on the peer-mapped window for
+    a derived target type (one peer copy per contiguous run on the fallback path)."""
     data, _ = _origin_stream(origin, origin_count, origin_type)
+    plan = _target_plan(target_count, target_type, data.numel())
+    if plan is not None:
+        win._plan_copy(True, data.to(_window_side(win, target_rank, data)), target_rank,
+                       int(target_disp) * win.disp_unit, plan)
+        _dt.COUNTERS["rma_kernel"] += 1
+        return SUCCESS
     pos = 0
     for off, n in _target_runs(win, target_disp, target_count, target_type, data.numel()):
         win._put_bytes(data[pos:pos + n], target_rank, off)
+        _dt.COUNTERS["rma_copies"] += 1
         pos += n
     return SUCCESS
 
@@ -478,10 +507,21 @@ def Get(origin, origin_count, origin_type, target_rank, target_disp, target_coun
     else:
         stage = origin_type.staging(origin, origin_count)
         unpack = (origin_type, stage, origin, int(origin_count))
-    pos = 0
-    for off, n in _target_runs(win, target_disp, target_count, target_type, stage.numel()):
-        win._get_bytes(stage[pos:pos + n], target_rank, off)
-        pos += n
+    plan = _target_plan(target_count, target_type, stage.numel())
+    if plan is not None:  # the whole target layout gathered by one launch on the peer-mapped window
+        side = _window_side(win, target_rank, stage)
+        land = stage if stage.device.type == side.type else torch.empty_like(stage, device=side)
+        win._plan_copy(False, land, target_rank, int(target_disp) * win.disp_unit, plan)
+        _dt.COUNTERS["rma_kernel"] += 1
+        if land is not stage:  # origin on the other side of the bus than the window: land, then cross
+            win.Flush()
+            stage.copy_(land)
+    else:
+        pos = 0
+        for off, n in _target_runs(win, target_disp, target_count, target_type, stage.numel()):
+            win._get_bytes(stage[pos:pos + n], target_rank, off)
+            _dt.COUNTERS["rma_copies"] += 1
+            pos += n
     if unpack is not None:  # derived origin: scatter once the data has landed
         win.Flush()
         t, st, buf, cnt = unpack

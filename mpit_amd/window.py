@@ -152,6 +152,24 @@ class Win:
     def _get_bytes(self, out: torch.Tensor, target_rank: int, byte_disp: int):
         self._w.get(out.data_ptr(), target_rank, int(byte_disp), out.numel() * out.element_size(), self._stream())
 
+    # plan-addressed forms: the target datatype's whole layout (datatypes.Plan) in ONE type_copy
+    # launch with the peer-mapped window as the strided side; `data` is the contiguous packed
+    # stream on the window's side (HBM for a device target, host memory for a host target).
+    # Complete, like every other operation, after the stream sync of Flush / Fence / Unlock.
+    def _plan_copy(self, put: bool, data: torch.Tensor, target_rank: int, byte_disp: int, plan):
+        if plan.total == 0:
+            return
+        if data.is_cuda != self._w.remote_device(target_rank) or not data.is_contiguous():
+            raise ValueError("one-sided plan copy: a contiguous packed stream on the target window's side is needed")
+        tab, off, table = plan.table(data.device)
+        base = int(byte_disp) + off  # a single run's offset moves into the base (no table)
+        unit = plan.unit(self._w.remote_ptr(target_rank) + base, data.data_ptr())
+        fn = self._w.put_plan if put else self._w.get_plan
+        fn(target_rank, base, list(plan.loops), tab, plan.R, plan.L, plan.per, unit, plan.lo - off, plan.hi - off,
+           data.data_ptr(), self._stream())
+        self._keep_all = getattr(self, "_keep_all", [])
+        self._keep_all.append((data, table))
+
     def _acc_elems(self, data: torch.Tensor, target_rank: int, byte_disp: int, a: float, b: float):
         self._w.accumulate(target_rank, int(byte_disp), data.data_ptr(), data.is_cuda, data.numel(),
                            data.dtype == torch.bfloat16, a, b, self._stream())
