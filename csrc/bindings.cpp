@@ -258,6 +258,36 @@ PYBIND11_MODULE(_mpit, m) {
       py::arg("stride"), py::arg("pad"), py::arg("dy"), py::arg("idx"), py::arg("dx"), py::arg("f32") = false,
       py::arg("ypool") = 0, py::arg("db") = 0, py::arg("ws") = 0);
   m.def("maxpool_bwd_ws_floats", &maxpool_bwd_ws_floats);
+  m.def("bn_pool_covered", &bn_pool_covered, py::arg("H"), py::arg("W"), py::arg("K"), py::arg("stride"),
+        py::arg("pad"));
+  m.def(
+      "bn_pool_fwd",
+      [](int dev, uintptr_t s, bool bf16, int N, int H, int W, int C, int K, int stride, int pad, uintptr_t x,
+         uintptr_t coef, uintptr_t y, uintptr_t idx, uintptr_t amax) {
+        bn_pool_fwd(dev, S(s), bf16, N, H, W, C, K, stride, pad, x, coef, y, idx, amax);
+      },
+      py::arg("dev"), py::arg("stream"), py::arg("bf16"), py::arg("N"), py::arg("H"), py::arg("W"), py::arg("C"),
+      py::arg("K"), py::arg("stride"), py::arg("pad"), py::arg("x"), py::arg("coef"), py::arg("y"), py::arg("idx"),
+      py::arg("amax") = 0);
+  m.def(
+      "pool_planes",
+      [](int dev, uintptr_t s, uintptr_t x, uintptr_t y, int64_t nel, uintptr_t ibound, uintptr_t obound) {
+        pool_planes(dev, S(s), x, y, nel, ibound, obound);
+      },
+      py::arg("dev"), py::arg("stream"), py::arg("x"), py::arg("y"), py::arg("nel"), py::arg("ibound"),
+      py::arg("obound"));
+  m.def(
+      "bn_pool_bwd",
+      [](int dev, uintptr_t s, bool bf16, int N, int H, int W, int C, int K, int stride, int pad, uintptr_t g,
+         uintptr_t idx, uintptr_t x, uintptr_t fcoef, uintptr_t gamma, uintptr_t mean, uintptr_t rstd, uintptr_t dx,
+         uintptr_t dgamma, uintptr_t dbeta, uintptr_t ws, uintptr_t amax) {
+        bn_pool_bwd(dev, S(s), bf16, N, H, W, C, K, stride, pad, g, idx, x, fcoef, gamma, mean, rstd, dx, dgamma, dbeta,
+                    ws, amax);
+      },
+      py::arg("dev"), py::arg("stream"), py::arg("bf16"), py::arg("N"), py::arg("H"), py::arg("W"), py::arg("C"),
+      py::arg("K"), py::arg("stride"), py::arg("pad"), py::arg("g"), py::arg("idx"), py::arg("x"), py::arg("fcoef"),
+      py::arg("gamma"), py::arg("mean"), py::arg("rstd"), py::arg("dx"), py::arg("dgamma"), py::arg("dbeta"),
+      py::arg("ws"), py::arg("amax") = 0);
   m.def(
       "avgpool_bwd",
       [](int dev, uintptr_t s, int N, int HW, int C, uintptr_t dy, uintptr_t dx, bool f32) {

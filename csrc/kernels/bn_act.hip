@@ -1135,7 +1135,553 @@ void bwd_impl(hipStream_t s, const T* dy, const uint8_t* mask, const T* x, T* dx
   hip_check(hipGetLastError(), "bn_act backward launch");
 }
 
+// ---------------------------------------------------------------- stem: BN + ReLU + max pool
+// pool(relu(bn(x))) as one op each way (kernels.h bn_pool_fwd / bn_pool_bwd): the BN output y,
+// its ReLU mask and the pool's input gradient dz are never in memory. Every kernel below
+// repeats the arithmetic and the order of the kernels it replaces (bn_apply_kernel ->
+// pool.hip maxpool_fwd_kernel; maxpool_bwd_kernel -> bn_bwd_reduce_kernel / bn_bwd_apply_kernel),
+// so its outputs have their bits.
+// Division of 0 <= n < 2^31 by a divisor known at launch: n / d = umulhi(n, mul) >> shr with
+// mul = ceil(2^(31 + ceil(log2 d)) / d) (d == 1: n itself). Integer divisions are emulated
+// (~25 instructions for 32 bits, far more for 64: pool.hip) and these kernels decompose one
+// pixel index per 8 channels: with plain divisions the backward passes were bound by their
+// integer arithmetic, not their bytes.
+struct FastDiv {
+  uint32_t d, mul, shr;
+};
+FastDiv fast_div(int d) {
+  FastDiv f{uint32_t(d), 0u, 0u};
+  if (d > 1) {
+    int l = 0;
+    while ((int64_t(1) << l) < d) ++l;
+    const int p = 31 + l;
+    f.mul = uint32_t(((uint64_t(1) << p) + uint32_t(d) - 1) / uint32_t(d));
+    f.shr = uint32_t(p - 32);
+  }
+  return f;
+}
+__device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv& f) {
+  return f.d == 1 ? n : __umulhi(n, f.mul) >> f.shr;
+}
+
+struct PoolGeo {
+  int N, H, W, C, Ho, Wo, K, stride, pad;
+  FastDiv dG, dC, dH, dW, dHo, dWo, dS;  // C / 8, C, H, W, Ho, Wo, stride
+};
+
+// index type of the pixel decompositions and element offsets: 32 bits while every element
+// index of the input tensor is below 2^31 (NARROW, host-checked)
+template <bool NARROW>
+using pidx_t = std::conditional_t<NARROW, uint32_t, int64_t>;
+
+// q = a / f.d, m = a % f.d
+template <bool NARROW>
+__device__ __forceinline__ pidx_t<NARROW> fdivq(pidx_t<NARROW> a, const FastDiv& f) {
+  if constexpr (NARROW) return fdiv(a, f);
+  else return a / int64_t(f.d);
+}
+template <bool NARROW>
+__device__ __forceinline__ void divmod(pidx_t<NARROW> a, const FastDiv& f, pidx_t<NARROW>& q, int& m) {
+  if constexpr (NARROW) q = fdiv(a, f);
+  else q = a / int64_t(f.d);
+  m = int(a - q * f.d);
+}
+
+// One thread owns 8 channels of one output pixel (maxpool_fwd_kernel's mapping, scan order and
+// comparison: first maximum wins, a NaN wins and propagates) and computes each window element
+// t = relu(x sc + sh) as bn_apply_kernel does; bf16: t rounded to bf16 before the comparison,
+// as the stored y was. Every input pixel lies in some window (host-checked), so the maximum
+// over the windows' elements is the maximum over y: the bound bn_apply_kernel raised.
+template <typename T, bool NARROW>
+__global__ __launch_bounds__(256) void bn_pool_fwd_kernel(const T* __restrict__ x, const float* __restrict__ coef,
+                                                          T* __restrict__ y, uint8_t* __restrict__ idx, PoolGeo g,
+                                                          int64_t total, AmaxOut am) {
+  using I = pidx_t<NARROW>;
+  const I t = I(blockIdx.x) * blockDim.x + threadIdx.x;
+  float mx = 0.f;
+  if (t < I(total)) {
+    I pix, r, n;
+    int c8, wo, ho;
+    divmod<NARROW>(t, g.dG, pix, c8);
+    divmod<NARROW>(pix, g.dWo, r, wo);
+    divmod<NARROW>(r, g.dHo, n, ho);
+    float sc[8], sh[8];
+    Vec<float>::load(coef + c8 * 8, sc);
+    Vec<float>::load(coef + g.C + c8 * 8, sh);
+    float best[8];
+    uint8_t arg[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      best[e] = -__builtin_inff();
+      arg[e] = 0;
+    }
+    const int h0 = ho * g.stride - g.pad, w0 = wo * g.stride - g.pad;
+    for (int i = 0; i < g.K; ++i) {
+      const int h = h0 + i;
+      if (unsigned(h) >= unsigned(g.H)) continue;
+      for (int j = 0; j < g.K; ++j) {
+        const int w = w0 + j;
+        if (unsigned(w) >= unsigned(g.W)) continue;
+        float fv[8];
+        Vec<T>::load(x + (((n * g.H + h) * g.W + w) * g.C + c8 * 8), fv);
+        const uint8_t k = uint8_t(i * g.K + j);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          float f = fmaxf(fmaf(fv[e], sc[e], sh[e]), 0.f);
+          mx = fmaxf(mx, fabsf(f));
+          if constexpr (sizeof(T) == 2) f = bf2f(f2bf(f));
+          if (f > best[e] || (f != f && best[e] == best[e])) {
+            best[e] = f;
+            arg[e] = k;
+          }
+        }
+      }
+    }
+    Vec<T>::store(y + (pix * g.C + c8 * 8), best);
+    uint2 a;
+    a.x = uint32_t(arg[0]) | (uint32_t(arg[1]) << 8) | (uint32_t(arg[2]) << 16) | (uint32_t(arg[3]) << 24);
+    a.y = uint32_t(arg[4]) | (uint32_t(arg[5]) << 8) | (uint32_t(arg[6]) << 16) | (uint32_t(arg[7]) << 24);
+    *reinterpret_cast<uint2*>(idx + (pix * g.C + c8 * 8)) = a;
+  }
+  if (am.amax) amax_finish(mx, am);
+}
+
+// fp32 values -> fp16 planes scaled by the slotted bound ibound (maxpool_fwd_kernel's planes
+// output, from values already pooled): the pooled maximum is exact only once the pass above
+// has ended, and a bound from the coefficients would change the exponent
+__global__ __launch_bounds__(256) void pool_planes_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                          int64_t nvec, const float* __restrict__ ibound,
+                                                          float* obound) {
+  const PlaneScale ps = plane_scale(slots_max_wave(ibound), obound);
+  const int64_t nel = nvec * 8;
+  uint16_t* yh = reinterpret_cast<uint16_t*>(y);
+  for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < nvec; i += int64_t(gridDim.x) * blockDim.x) {
+    float v[8];
+    Vec<float>::load(x + i * 8, v);
+    uint32_t hw[4], lw[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) split_pair(v[2 * p], v[2 * p + 1], ps, hw[p], lw[p]);
+    *reinterpret_cast<uint4*>(yh + i * 8) = make_uint4(hw[0], hw[1], hw[2], hw[3]);
+    *reinterpret_cast<uint4*>(yh + nel + i * 8) = make_uint4(lw[0], lw[1], lw[2], lw[3]);
+  }
+}
+
+// CH (8, or 4 of fp32) consecutive channels' argmax bytes and gradients of one output pixel
+template <int CH>
+__device__ __forceinline__ void ld_arg(const uint8_t* __restrict__ p, uint32_t (&w)[CH / 4]) {
+  if constexpr (CH == 8) {
+    const uint2 a = *reinterpret_cast<const uint2*>(p);
+    w[0] = a.x;
+    w[1] = a.y;
+  } else {
+    w[0] = *reinterpret_cast<const uint32_t*>(p);
+  }
+}
+template <typename T, int CH>
+__device__ __forceinline__ void ld_ch(const T* __restrict__ p, float (&v)[CH]) {
+  if constexpr (CH == 8) {
+    Vec<T>::load(p, v);
+  } else {
+    static_assert(sizeof(T) == 4, "4-channel pieces are fp32");
+    const float4 r = *reinterpret_cast<const float4*>(p);
+    v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
+  }
+}
+
+// The NW x NW candidate windows of input pixel (n, h, w) (ceil(K / stride) <= NW), in ho, then
+// wo ascending: o = the window's element offset at channel 0, k = the pixel's index in the
+// window or -1 when the candidate is no window of this pixel (it then re-reads a valid window
+// and is not taken). Shared by every channel piece of the pixel.
+template <int NW, bool NARROW>
+struct PoolWin {
+  pidx_t<NARROW> o[NW * NW];
+  int k[NW * NW];
+};
+template <int NW, bool NARROW>
+__device__ __forceinline__ void pool_win(const PoolGeo& g, pidx_t<NARROW> n, int h, int w, PoolWin<NW, NARROW>& win) {
+  // output windows containing h: ho*stride - pad <= h <= ho*stride - pad + K - 1
+  // (max(0, a / stride) with C's division is 0 for every a <= 0)
+  const int ah = h + g.pad - g.K + g.stride, aw = w + g.pad - g.K + g.stride;
+  const int hlo = ah > 0 ? int(fdiv(uint32_t(ah), g.dS)) : 0, hhi = min(g.Ho - 1, int(fdiv(uint32_t(h + g.pad), g.dS)));
+  const int wlo = aw > 0 ? int(fdiv(uint32_t(aw), g.dS)) : 0, whi = min(g.Wo - 1, int(fdiv(uint32_t(w + g.pad), g.dS)));
+#pragma unroll
+  for (int p = 0; p < NW; ++p) {
+    const int ho = hlo + p, i = h - (ho * g.stride - g.pad);
+    const bool okh = ho <= hhi && i >= 0 && i < g.K;
+#pragma unroll
+    for (int q = 0; q < NW; ++q) {
+      const int wo = wlo + q, j = w - (wo * g.stride - g.pad);
+      const bool ok = okh && wo <= whi && j >= 0 && j < g.K;
+      win.o[p * NW + q] = ((n * g.Ho + min(ho, g.Ho - 1)) * g.Wo + min(wo, g.Wo - 1)) * g.C;
+      win.k[p * NW + q] = ok ? i * g.K + j : -1;
+    }
+  }
+}
+// channels [c0, c0 + CH) of the gather over the candidates: every load issued before the first
+// use, acc += gy where the window's argmax is this pixel; bf16: the sum rounded as it was stored
+template <typename T, int NW, bool NARROW, int CH>
+__device__ __forceinline__ void pool_take(const T* __restrict__ gy, const uint8_t* __restrict__ idx,
+                                          const PoolWin<NW, NARROW>& win, int c0, float (&acc)[CH]) {
+  uint32_t a[NW * NW][CH / 4];
+  float gv[NW * NW][CH];
+#pragma unroll
+  for (int c = 0; c < NW * NW; ++c) {
+    ld_arg<CH>(idx + (win.o[c] + c0), a[c]);
+    ld_ch<T, CH>(gy + (win.o[c] + c0), gv[c]);
+  }
+#pragma unroll
+  for (int e = 0; e < CH; ++e) acc[e] = 0.f;
+#pragma unroll
+  for (int c = 0; c < NW * NW; ++c)
+#pragma unroll
+    for (int e = 0; e < CH; ++e) {
+      const int ae = int((a[c][e >> 2] >> (8 * (e & 3))) & 0xff);
+      if (ae == win.k[c]) acc[e] += gv[c][e];
+    }
+  if constexpr (sizeof(T) == 2) {
+#pragma unroll
+    for (int e = 0; e < CH; ++e) acc[e] = bf2f(f2bf(acc[e]));
+  }
+}
+
+// The pool's input gradient at pixel (n, h, w), channels [c0, c0 + CH): maxpool_bwd_kernel's
+// gather — the windows that contain the pixel in ho, then wo ascending, acc += gy where the
+// window's argmax is this pixel; bf16: the sum rounded to bf16, as it was stored.
+// NW > 0: at most NW x NW windows contain a pixel (ceil(K / stride) <= NW): every load is
+// issued before the first use; a candidate past the range re-reads a valid window and is not
+// taken. NW == 0: any geometry, window by window.
+template <typename T, int NW, bool NARROW, int CH>
+__device__ __forceinline__ void pool_gather(const T* __restrict__ gy, const uint8_t* __restrict__ idx,
+                                            const PoolGeo& g, pidx_t<NARROW> n, int h, int w, int c0,
+                                            float (&acc)[CH]) {
+  using I = pidx_t<NARROW>;
+  if constexpr (NW > 0) {
+    PoolWin<NW, NARROW> win;
+    pool_win<NW, NARROW>(g, n, h, w, win);
+    pool_take<T, NW, NARROW, CH>(gy, idx, win, c0, acc);
+  } else {
+#pragma unroll
+    for (int e = 0; e < CH; ++e) acc[e] = 0.f;
+    const int ah = h + g.pad - g.K + g.stride, aw = w + g.pad - g.K + g.stride;  // (as pool_win)
+    const int hlo = ah > 0 ? int(fdiv(uint32_t(ah), g.dS)) : 0, hhi = min(g.Ho - 1, int(fdiv(uint32_t(h + g.pad), g.dS)));
+    const int wlo = aw > 0 ? int(fdiv(uint32_t(aw), g.dS)) : 0, whi = min(g.Wo - 1, int(fdiv(uint32_t(w + g.pad), g.dS)));
+    for (int ho = hlo; ho <= hhi; ++ho) {
+      const int i = h - (ho * g.stride - g.pad);
+      if (i < 0 || i >= g.K) continue;
+      for (int wo = wlo; wo <= whi; ++wo) {
+        const int j = w - (wo * g.stride - g.pad);
+        if (j < 0 || j >= g.K) continue;
+        const I o = ((n * g.Ho + ho) * g.Wo + wo) * g.C + c0;
+        uint32_t a[CH / 4];
+        float gv[CH];
+        ld_arg<CH>(idx + o, a);
+        ld_ch<T, CH>(gy + o, gv);
+        const int k = i * g.K + j;
+#pragma unroll
+        for (int e = 0; e < CH; ++e) {
+          const int ae = int((a[e >> 2] >> (8 * (e & 3))) & 0xff);
+          if (ae == k) acc[e] += gv[e];
+        }
+      }
+    }
+    if constexpr (sizeof(T) == 2) {
+#pragma unroll
+      for (int e = 0; e < CH; ++e) acc[e] = bf2f(f2bf(acc[e]));
+    }
+  }
+}
+
+// dz of row r of the [M, C] view of x, channels [c0, c0 + CH): the gather above, masked by
+// bn(x) > 0 — the bit bn_apply_kernel stored in the ReLU mask, from the x the pass reads anyway
+template <typename T, int NW, bool NARROW, int CH>
+__device__ __forceinline__ void pool_dz(const T* __restrict__ gy, const uint8_t* __restrict__ idx, const PoolGeo& g,
+                                        pidx_t<NARROW> r, int c0, const float (&xx)[CH], const float (&sc)[CH],
+                                        const float (&sh)[CH], float (&dz)[CH]) {
+  pidx_t<NARROW> q, n;
+  int h, w;
+  divmod<NARROW>(r, g.dW, q, w);
+  divmod<NARROW>(q, g.dH, n, h);
+  pool_gather<T, NW, NARROW, CH>(gy, idx, g, n, h, w, c0, dz);
+#pragma unroll
+  for (int v = 0; v < CH; ++v) dz[v] = fmaf(xx[v], sc[v], sh[v]) > 0.f ? dz[v] : 0.f;
+}
+
+// bn_bwd_reduce_kernel<T, true> with dz computed (pool_dz) instead of loaded: the same blocks,
+// the same rows per thread, the same LDS combine and partials layout. A thread adds its rows
+// r0 + rs, + R, ... one after the other in ascending order — in that kernel's two-row loop and
+// remainder loop as well — so batching the loads of four rows (fp32: three; then two, then
+// one) leaves the order of every addition what it was; it keeps more loads in flight, which
+// the 2 waves per SIMD of stat_blocks' grid need now that a row costs a gather. MAXT: the block size bound
+// (256 lets the NW x NW gathers of four rows stay in registers; 2 waves per SIMD: the grid's two
+// blocks per CU run side by side).
+template <typename T, int NW, int MAXT, bool NARROW>
+__global__ __launch_bounds__(MAXT, 2) void bn_pool_bwd_reduce_kernel(const T* __restrict__ gy,
+                                                                  const uint8_t* __restrict__ idx,
+                                                                  const T* __restrict__ x,
+                                                                  const float* __restrict__ fcoef,
+                                                                  const float* __restrict__ mean, PoolGeo geo,
+                                                                  int64_t M, int64_t rows_per_block,
+                                                                  float* __restrict__ part) {
+  using I = pidx_t<NARROW>;
+  constexpr int V = Vec<T>::N;
+  extern __shared__ float lds[];
+  const int C = geo.C;
+  const int G = C / V;
+  const int g = threadIdx.x % G, rs = threadIdx.x / G, R = blockDim.x / G;
+  float mu[V], s1[V], s2[V], sc[V], sh[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    mu[v] = mean[g * V + v];
+    sc[v] = fcoef[g * V + v];
+    sh[v] = fcoef[C + g * V + v];
+    s1[v] = s2[v] = 0.f;
+  }
+  const int64_t r0 = int64_t(blockIdx.x) * rows_per_block;
+  const int64_t r1 = min(M, r0 + rows_per_block);
+  int64_t r = r0 + rs;
+  // rows r, r + R, ..., r + (U - 1) R: all loads, then the additions row by row
+  auto rows = [&](auto nu) {
+    constexpr int U = decltype(nu)::value;
+    float d[U][V], xx[U][V];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const I ru = I(r + u * R);
+      Vec<T>::load(x + (ru * C + g * V), xx[u]);
+      pool_dz<T, NW, NARROW, V>(gy, idx, geo, ru, g * V, xx[u], sc, sh, d[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        const float dz = d[u][v];
+        s1[v] += dz;
+        s2[v] = fmaf(dz, xx[u][v] - mu[v], s2[v]);
+      }
+  };
+  constexpr int UB = sizeof(T) == 4 ? 3 : 4;  // (four fp32 rows spill at 2 waves per SIMD)
+  if constexpr (MAXT <= 256)
+    for (; r + (UB - 1) * R < r1; r += UB * R) rows(std::integral_constant<int, UB>{});
+  for (; r + R < r1; r += 2 * R) rows(std::integral_constant<int, 2>{});
+  for (; r < r1; r += R) rows(std::integral_constant<int, 1>{});
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    lds[(rs * 2 + 0) * C + g * V + v] = s1[v];
+    lds[(rs * 2 + 1) * C + g * V + v] = s2[v];
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += blockDim.x) {
+    float a = 0.f, b = 0.f;
+    for (int k = 0; k < R; ++k) {
+      a += lds[(k * 2 + 0) * C + c];
+      b += lds[(k * 2 + 1) * C + c];
+    }
+    part[(size_t(blockIdx.x) * 2 + 0) * C + c] = a;
+    part[(size_t(blockIdx.x) * 2 + 1) * C + c] = b;
+  }
+}
+
+// bn_bwd_apply_kernel<T, true, false> with dz computed: dx = A dz + Cc x + B, element by
+// element. The pass is bound by its integer arithmetic (pixel decomposition, windows,
+// offsets), not by its bytes, so a thread does that once for a pixel and then NP channel
+// pieces of it (CH = 4 fp32 / 8 bf16 channels: 16-byte accesses): L = C / (CH NP) lanes per
+// pixel, lane j takes the pieces j, j + L, ..., so each instruction of L lanes covers
+// 16 L contiguous bytes (whole 128-byte lines for C = 64). dL divides by L. For L | 256 a
+// thread walks a few pixels by a grid stride that keeps it on its channels, so the five
+// coefficient vectors (more bytes through L1 than x and the gather together) load once.
+template <typename T, int NW, bool NARROW, int NP>
+__global__ __launch_bounds__(256) void bn_pool_bwd_apply_kernel(const T* __restrict__ gy,
+                                                                const uint8_t* __restrict__ idx,
+                                                                const T* __restrict__ x,
+                                                                const float* __restrict__ fcoef,
+                                                                const float* __restrict__ coef, T* __restrict__ dx,
+                                                                PoolGeo geo, FastDiv dL, int64_t nthr, AmaxOut am) {
+  using I = pidx_t<NARROW>;
+  constexpr int CH = sizeof(T) == 4 ? 4 : 8;
+  const int C = geo.C;
+  const I t0 = I(blockIdx.x) * blockDim.x + threadIdx.x;
+  const I stride = I(gridDim.x) * blockDim.x;  // a multiple of L (host-checked): j stays
+  float mx = 0.f;
+  I r0;
+  int j;
+  divmod<NARROW>(t0, dL, r0, j);
+  // the thread's coefficients: its channels are the same in every round
+  float A[NP][CH], Cc[NP][CH], B[NP][CH], sc[NP][CH], sh[NP][CH];
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    const int c0 = (p * int(dL.d) + j) * CH;
+    ld_ch<float, CH>(fcoef + c0, sc[p]);
+    ld_ch<float, CH>(fcoef + C + c0, sh[p]);
+    ld_ch<float, CH>(coef + c0, A[p]);
+    ld_ch<float, CH>(coef + C + c0, Cc[p]);
+    ld_ch<float, CH>(coef + 2 * C + c0, B[p]);
+  }
+  for (I t = t0; t < I(nthr); t += stride) {
+    I q, n;
+    int h, w;
+    const I r = fdivq<NARROW>(t, dL);
+    divmod<NARROW>(r, geo.dW, q, w);
+    divmod<NARROW>(q, geo.dH, n, h);
+    [[maybe_unused]] PoolWin<(NW > 0 ? NW : 1), NARROW> win;
+    if constexpr (NW > 0) pool_win<NW, NARROW>(geo, n, h, w, win);
+    float xx[NP][CH], dz[NP][CH];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      const int c0 = (p * int(dL.d) + j) * CH;
+      ld_ch<T, CH>(x + (r * C + c0), xx[p]);
+      if constexpr (NW > 0) pool_take<T, NW, NARROW, CH>(gy, idx, win, c0, dz[p]);
+      else pool_gather<T, NW, NARROW, CH>(gy, idx, geo, n, h, w, c0, dz[p]);
+    }
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      const int c0 = (p * int(dL.d) + j) * CH;
+#pragma unroll
+      for (int v = 0; v < CH; ++v) {
+        const float d = fmaf(xx[p][v], sc[p][v], sh[p][v]) > 0.f ? dz[p][v] : 0.f;  // (pool_dz's mask)
+        xx[p][v] = fmaf(A[p][v], d, fmaf(Cc[p][v], xx[p][v], B[p][v]));
+        mx = fmaxf(mx, fabsf(xx[p][v]));
+      }
+      if constexpr (CH == 8) Vec<T>::store(dx + (r * C + c0), xx[p]);
+      else *reinterpret_cast<float4*>(dx + (r * C + c0)) = make_float4(xx[p][0], xx[p][1], xx[p][2], xx[p][3]);
+    }
+  }
+  if (am.amax) amax_finish(mx, am);
+}
+
+PoolGeo bn_pool_geo(int N, int H, int W, int C, int K, int stride, int pad) {
+  if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 || K <= 0 || K > 15 || stride <= 0 || pad < 0 || 2 * pad > K)
+    throw std::invalid_argument("bn_pool: unsupported geometry (C % 8 == 0, K <= 15, pad <= K/2)");
+  if (!bn_pool_covered(H, W, K, stride, pad))
+    throw std::invalid_argument("bn_pool: the windows must cover every input pixel");
+  PoolGeo g{N, H, W, C, (H + 2 * pad - K) / stride + 1, (W + 2 * pad - K) / stride + 1, K, stride, pad};
+  g.dG = fast_div(C / 8);
+  g.dC = fast_div(C);
+  g.dH = fast_div(H);
+  g.dW = fast_div(W);
+  g.dHo = fast_div(g.Ho);
+  g.dWo = fast_div(g.Wo);
+  g.dS = fast_div(stride);
+  return g;
+}
+
+// 32-bit index arithmetic (and the multiply-shift divisions) while no element index of the
+// input tensor, one block of padding included, reaches 2^31
+bool pool_narrow(const PoolGeo& g) { return int64_t(g.N) * g.H * g.W * g.C + 2048 < (int64_t(1) << 31); }
+
+template <typename T>
+void bn_pool_fwd_t(hipStream_t s, const PoolGeo& g, uintptr_t x, uintptr_t coef, uintptr_t y, uintptr_t idx,
+                   uintptr_t amax) {
+  const int64_t total = int64_t(g.N) * g.Ho * g.Wo * (g.C / 8);
+  const int64_t blocks = (total + 255) / 256;
+  if (blocks > INT32_MAX) throw std::invalid_argument("bn_pool_fwd: tensor too large");
+  auto* k = pool_narrow(g) ? bn_pool_fwd_kernel<T, true> : bn_pool_fwd_kernel<T, false>;
+  hipLaunchKernelGGL(k, dim3(unsigned(blocks)), dim3(256), 0, s, reinterpret_cast<const T*>(x),
+                     reinterpret_cast<const float*>(coef), reinterpret_cast<T*>(y), reinterpret_cast<uint8_t*>(idx), g,
+                     total, AmaxOut{reinterpret_cast<float*>(amax)});
+  hip_check(hipGetLastError(), "bn_pool_fwd launch");
+}
+
+template <typename T>
+void bn_pool_bwd_t(hipStream_t s, const PoolGeo& geo, const T* gy, const uint8_t* idx, const T* x, const float* fcoef,
+                   const float* gamma, const float* mean, const float* rstd, T* dx, float* dgamma, float* dbeta,
+                   float* ws, uintptr_t amax) {
+  constexpr int V = Vec<T>::N;
+  const int C = geo.C;
+  const int64_t M = int64_t(geo.N) * geo.H * geo.W;
+  check_shape(M, C, V, reinterpret_cast<uintptr_t>(x));
+  const int G = C / V;
+  const int blk = block_for(G);
+  const int R = blk / G;
+  int64_t rpb;
+  const int nb = stat_blocks(M, R, &rpb);
+  float* part = ws + 3 * C;
+  const size_t shm = size_t(R) * 2 * C * sizeof(float);
+  // apply pass: NP = 2 channel pieces per thread when the channels allow
+  constexpr int CH = sizeof(T) == 4 ? 4 : 8;
+  const int np = C % (CH * 2) == 0 ? 2 : 1;
+  const int L = C / (CH * np);
+  const int64_t nthr = M * L;
+  // kApplyRounds pixels per thread (grid stride) when the stride keeps a thread on its channels
+  constexpr int kApplyRounds = 4;
+  const int64_t blocks = 256 % L == 0 ? (nthr + 256 * kApplyRounds - 1) / (256 * kApplyRounds) : (nthr + 255) / 256;
+  if (blocks > INT32_MAX) throw std::invalid_argument("bn_pool_bwd: tensor too large");
+  const bool narrow = pool_narrow(geo);
+  const bool nw2 = (geo.K + geo.stride - 1) / geo.stride <= 2;  // at most 2 x 2 windows per pixel
+  {
+    auto* k = nw2 && blk <= 256 ? (narrow ? bn_pool_bwd_reduce_kernel<T, 2, 256, true> : bn_pool_bwd_reduce_kernel<T, 2, 256, false>)
+                                : (narrow ? bn_pool_bwd_reduce_kernel<T, 0, 1024, true> : bn_pool_bwd_reduce_kernel<T, 0, 1024, false>);
+    hipLaunchKernelGGL(k, dim3(nb), dim3(blk), shm, s, gy, idx, x, fcoef, mean, geo, M, rpb, part);
+  }
+  // (bn_finalize_bwd_kernel, not the tile finalize: that one combines in another order)
+  hipLaunchKernelGGL(bn_finalize_bwd_kernel, dim3((C + kFinCh - 1) / kFinCh), dim3(kFinCh * kFinK), 0, s, part, nb, C,
+                     M, gamma, mean, rstd, dgamma, dbeta, ws);
+  if (amax) hip_check(hipMemsetAsync(reinterpret_cast<void*>(amax), 0, kBoundFloats * sizeof(float), s), "amax zero");
+  const AmaxOut am{reinterpret_cast<float*>(amax)};
+  auto apply = [&](auto nw, auto nr, auto npc) {
+    hipLaunchKernelGGL((bn_pool_bwd_apply_kernel<T, decltype(nw)::value, decltype(nr)::value, decltype(npc)::value>),
+                       dim3(unsigned(blocks)), dim3(256), 0, s, gy, idx, x, fcoef, static_cast<const float*>(ws), dx,
+                       geo, fast_div(L), nthr, am);
+  };
+  auto apply_np = [&](auto nw, auto nr) {
+    if (np == 2) apply(nw, nr, std::integral_constant<int, 2>{});
+    else apply(nw, nr, std::integral_constant<int, 1>{});
+  };
+  auto apply_nr = [&](auto nw) {
+    if (narrow) apply_np(nw, std::true_type{});
+    else apply_np(nw, std::false_type{});
+  };
+  if (nw2) apply_nr(std::integral_constant<int, 2>{});
+  else apply_nr(std::integral_constant<int, 0>{});
+  hip_check(hipGetLastError(), "bn_pool_bwd launch");
+}
+
 }  // namespace
+
+bool bn_pool_covered(int H, int W, int K, int stride, int pad) {
+  if (H <= 0 || W <= 0 || K <= 0 || stride <= 0 || pad < 0) return false;
+  const int Ho = (H + 2 * pad - K) / stride + 1, Wo = (W + 2 * pad - K) / stride + 1;
+  if (H + 2 * pad < K || W + 2 * pad < K) return false;
+  return (Ho - 1) * stride - pad + K - 1 >= H - 1 && (Wo - 1) * stride - pad + K - 1 >= W - 1;
+}
+
+void bn_pool_fwd(int dev, hipStream_t s, bool bf16, int N, int H, int W, int C, int K, int stride, int pad,
+                 uintptr_t x, uintptr_t coef, uintptr_t y, uintptr_t idx, uintptr_t amax) {
+  const PoolGeo g = bn_pool_geo(N, H, W, C, K, stride, pad);
+  if (!x || !coef || !y || !idx || (x | y | coef) % 16 || idx % 8)
+    throw std::invalid_argument("bn_pool_fwd: missing or misaligned buffers");
+  hip_check(hipSetDevice(dev), "hipSetDevice");
+  if (bf16) bn_pool_fwd_t<uint16_t>(s, g, x, coef, y, idx, amax);
+  else bn_pool_fwd_t<float>(s, g, x, coef, y, idx, amax);
+}
+
+void pool_planes(int dev, hipStream_t s, uintptr_t x, uintptr_t y, int64_t nel, uintptr_t ibound, uintptr_t obound) {
+  if (nel <= 0 || nel % 8 || !x || !y || x == y || (x | y) % 16 || (nel * 2) % 16 || !ibound || !obound)
+    throw std::invalid_argument("pool_planes: needs nel % 8 == 0, two aligned buffers and both bounds");
+  hip_check(hipSetDevice(dev), "hipSetDevice");
+  const int64_t nvec = nel / 8;
+  const unsigned grid = unsigned(std::min<int64_t>((nvec + 255) / 256, 65536));
+  hipLaunchKernelGGL(pool_planes_kernel, dim3(grid), dim3(256), 0, s, reinterpret_cast<const float*>(x),
+                     reinterpret_cast<float*>(y), nvec, reinterpret_cast<const float*>(ibound),
+                     reinterpret_cast<float*>(obound));
+  hip_check(hipGetLastError(), "pool_planes launch");
+}
+
+void bn_pool_bwd(int dev, hipStream_t s, bool bf16, int N, int H, int W, int C, int K, int stride, int pad,
+                 uintptr_t g, uintptr_t idx, uintptr_t x, uintptr_t fcoef, uintptr_t gamma, uintptr_t mean,
+                 uintptr_t rstd, uintptr_t dx, uintptr_t dgamma, uintptr_t dbeta, uintptr_t ws, uintptr_t amax) {
+  const PoolGeo geo = bn_pool_geo(N, H, W, C, K, stride, pad);
+  if (!g || !idx || !x || !fcoef || !mean || !rstd || !dx || !ws || (g | x | dx | fcoef | ws) % 16 || idx % 8)
+    throw std::invalid_argument("bn_pool_bwd: missing or misaligned buffers");
+  hip_check(hipSetDevice(dev), "hipSetDevice");
+  auto F = [](uintptr_t p) { return reinterpret_cast<float*>(p); };
+  const auto* ix = reinterpret_cast<const uint8_t*>(idx);
+  if (bf16)
+    bn_pool_bwd_t<uint16_t>(s, geo, reinterpret_cast<const uint16_t*>(g), ix, reinterpret_cast<const uint16_t*>(x),
+                            F(fcoef), F(gamma), F(mean), F(rstd), reinterpret_cast<uint16_t*>(dx), F(dgamma),
+                            F(dbeta), F(ws), amax);
+  else
+    bn_pool_bwd_t<float>(s, geo, reinterpret_cast<const float*>(g), ix, reinterpret_cast<const float*>(x), F(fcoef),
+                         F(gamma), F(mean), F(rstd), reinterpret_cast<float*>(dx), F(dgamma), F(dbeta), F(ws), amax);
+}
 
 int64_t bn_workspace_floats(int C) { return int64_t(3) * C + int64_t(2) * kMaxStatBlocks * C; }
 

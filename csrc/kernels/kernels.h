@@ -342,6 +342,27 @@ void maxpool_bwd(int dev, hipStream_t s, int N, int H, int W, int C, int K, int 
                  uintptr_t idx, uintptr_t dx, bool f32 = false, uintptr_t ypool = 0, uintptr_t db = 0,
                  uintptr_t ws = 0);
 int64_t maxpool_bwd_ws_floats(int C);
+
+// ---- stem: BN + ReLU + max pool as one op each way (bn_act.hip) ------------------------
+// pool(relu(bn(x))) without the BN output, its ReLU mask or the pool's input gradient in memory.
+// Only for windows that cover every input pixel (bn_pool_covered): then the maximum over the
+// pooled values is the maximum over the BN output, today's bound.
+bool bn_pool_covered(int H, int W, int K, int stride, int pad);
+// x [N,H,W,C] (the conv output), coef [2][C] (scale, shift: bn_act_fwd with y == 0, or a
+// folded finalize) -> y [N,Ho,Wo,C] plain bf16 / fp32 and idx as maxpool_fwd; amax (optional,
+// zeroed by the finalize): raised to the exact max |relu(bn(x))|.
+void bn_pool_fwd(int dev, hipStream_t s, bool bf16, int N, int H, int W, int C, int K, int stride, int pad,
+                 uintptr_t x, uintptr_t coef, uintptr_t y, uintptr_t idx, uintptr_t amax = 0);
+// fp32 x [nel] -> y as fp16 planes (planes.h) scaled by the slotted bound ibound, which obound
+// receives in slot 0 (maxpool_fwd's planes output, from values already pooled)
+void pool_planes(int dev, hipStream_t s, uintptr_t x, uintptr_t y, int64_t nel, uintptr_t ibound, uintptr_t obound);
+// g [N,Ho,Wo,C]: the gradient of the pooled output; x, fcoef: the forward's; dx [N,H,W,C],
+// dgamma, dbeta and amax (max |dx|) as bn_act_bwd with relu; ws: bn_workspace_floats(C).
+// dz = the pool's gather (maxpool_bwd) masked by bn(x) > 0, computed in both passes instead of
+// stored; the reduce pass adds in bn_act_bwd's order, so every output has its bits.
+void bn_pool_bwd(int dev, hipStream_t s, bool bf16, int N, int H, int W, int C, int K, int stride, int pad,
+                 uintptr_t g, uintptr_t idx, uintptr_t x, uintptr_t fcoef, uintptr_t gamma, uintptr_t mean,
+                 uintptr_t rstd, uintptr_t dx, uintptr_t dgamma, uintptr_t dbeta, uintptr_t ws, uintptr_t amax = 0);
 // global average pool backward over NHWC: dx[n][p][c] = dy[n][c] / HW (bf16 / fp32)
 void avgpool_bwd(int dev, hipStream_t s, int N, int HW, int C, uintptr_t dy, uintptr_t dx, bool f32 = false);
 

@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 
 from ..ops.bn import BatchNormAct2d, bn_pair
+from ..ops.bn_pool import bn_relu_pool
 from ..ops.conv import Conv1x1, ConvNHWC, GradSlot, StemConv, feeds_bn, park_grad
 from ..ops.linear import LinearAct
 from ..ops.pool import GlobalAvgPoolNHWC, MaxPool2dNHWC
@@ -222,7 +223,9 @@ class ResNet(nn.Module):
 
     def forward(self, x):
         if isinstance(self.bn1, BatchNormAct2d):
-            x = self.maxpool(self.bn1(self.conv1(x)))
+            # BN + ReLU + max pool as one op each way where the kernels allow (ops/bn_pool.py),
+            # else maxpool(bn1(.))
+            x = bn_relu_pool(self.bn1, self.maxpool, self.conv1(x))
         else:
             x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
