@@ -210,6 +210,14 @@ PYBIND11_MODULE(_mpit, m) {
   m.def("bound_floats", [] { return kBoundFloats; });
   m.def("gemm_tn_supported", &gemm_tn_supported);
   m.def("gemm_tn_ws_floats", &gemm_tn_ws_floats);
+  m.def("gemm_nt_plan", &gemm_nt_plan, py::arg("f32"), py::arg("M"), py::arg("N"), py::arg("K"), py::arg("C") = 0,
+        py::arg("pitch") = 0, py::arg("ostr") = 1, py::arg("epi") = 0, py::arg("lda") = 0, py::arg("ldb") = 0,
+        py::arg("bps") = 0, py::arg("amax_a") = false, py::arg("amax_b") = false, py::arg("aps") = 0);
+  m.def("gemm_tn_plan", &gemm_tn_plan, py::arg("dev"), py::arg("f32"), py::arg("M"), py::arg("N"), py::arg("K"),
+        py::arg("C") = 0, py::arg("pitch") = 0, py::arg("beta") = 0.f, py::arg("ws") = true, py::arg("amax_y") = false,
+        py::arg("amax_x") = false, py::arg("yps") = 0, py::arg("xps") = 0);
+  m.def("gemm_nt_built", &gemm_nt_built);
+  m.def("gemm_tn_built", &gemm_tn_built);
   m.def("device_cu_count", &device_cu_count);
   m.def("stream_create_cu_masked", &stream_create_cu_masked);
   m.def(

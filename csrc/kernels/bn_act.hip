@@ -128,10 +128,7 @@ struct Slot {
 
 // MPIT_BN_SPLIT=0 keeps the unsplit fp32 layout (A/B knob)
 inline bool split_ok(bool f32, int C, int blk) {
-  static const bool on = [] {
-    const char* e = std::getenv("MPIT_BN_SPLIT");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = !env_off("MPIT_BN_SPLIT");
   return on && f32 && blk == 256 && 2048 % C == 0;
 }
 
@@ -165,10 +162,7 @@ __device__ __forceinline__ void for_slots(int64_t i, int64_t stride, int64_t nve
 // the grid-stride loop over <= 4096 blocks (0) and 4 (profiles/bn_apply_passes_r04.md);
 // MPIT_BN_APPLY_U overrides (0, 1, 2).
 inline int apply_u(bool f32) {
-  static const int u = [] {
-    const char* e = std::getenv("MPIT_BN_APPLY_U");
-    return e ? std::atoi(e) : -1;
-  }();
+  static const int u = env_int("MPIT_BN_APPLY_U", -1);
   return u >= 0 ? u : (f32 ? 1 : 2);
 }
 
@@ -638,10 +632,7 @@ void launch_tiles_finalize(hipStream_t s, const float* part, int64_t nt, int C, 
   uint32_t* tick = base + size_t(launches.fetch_add(1) % kTicketSlots) * kMaxChBlocks;
   int rpg;
   const int g = tile_groups(nt, &rpg);
-  static const bool wide = [] {
-    const char* e = std::getenv("MPIT_BN_FIN_LANES");
-    return e && std::atoi(e) == 16;
-  }();
+  static const bool wide = env_int("MPIT_BN_FIN_LANES", 0) == 16;
   if (wide)
     hipLaunchKernelGGL((bn_tiles_finalize_kernel<T, CHAN, kFinLanesWide>), dim3(nchb, g), dim3(64 * kFinLanesWide), 0,
                        s, part, int(nt), C, M, x, rpg, lvl, tick, fa);

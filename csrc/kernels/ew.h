@@ -31,6 +31,8 @@
 #include <vector>
 #include <algorithm>
 
+#include "env.h"
+
 #define MPIT_HD __host__ __device__ __forceinline__
 
 namespace mpit {
@@ -209,8 +211,8 @@ void run_host(const Arrays<NA>& a, int64_t n, const F& f) {
 
 // (unroll, grid cap) for n4 float4 groups; MPIT_EW_UNROLL / MPIT_EW_GRID override (A/B).
 inline void pick_shape(int64_t n4, int& unroll, int64_t& cap) {
-  static const int env_u = [] { const char* e = std::getenv("MPIT_EW_UNROLL"); return e ? std::atoi(e) : 0; }();
-  static const int64_t env_g = [] { const char* e = std::getenv("MPIT_EW_GRID"); return e ? std::atoll(e) : 0; }();
+  static const int env_u = env_int("MPIT_EW_UNROLL", 0);
+  static const int64_t env_g = env_i64("MPIT_EW_GRID", 0);
   unroll = n4 <= (int64_t(1) << 21) ? 1 : (n4 <= (int64_t(1) << 23) ? 2 : 4);
   cap = n4 <= (int64_t(1) << 21) ? int64_t(1) << 30 : kMaxGrid;
   if (env_u == 1 || env_u == 2 || env_u == 4) unroll = env_u;

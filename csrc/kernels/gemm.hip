@@ -48,7 +48,11 @@
 #include <vector>
 #include <stdexcept>
 #include <string>
+#include <tuple>
+#include <type_traits>
+#include <utility>
 
+#include "env.h"
 #include "ew.h"
 #include "kernels.h"
 
@@ -244,6 +248,35 @@ struct ConvGeo {
 
 enum { EPI_NONE = 0, EPI_STATS = 1, EPI_BNRED = 2, EPI_BNRED2 = 3, EPI_RELUB = 4 };
 
+// Format mode FM of the fp32 kernels (an int template argument; 16-bit element types run
+// FM_NATIVE, and gemm_tn's FM_F16_PLANES is a 16-bit kernel fed fp32 data as fp16 planes)
+enum {
+  FM_NATIVE = 0,         // the element type's own MFMA: bf16, or fp32 on v_mfma_f32_32x32x2_f32
+  FM_X6_K16 = 1,         // bf16x6: both operands split in registers into 3 bf16 planes, 16-deep k-tiles
+  FM_X6_K32 = 3,         // bf16x6 on 32-deep k-tiles (128-B LDS rows)
+  FM_BPLANES_W22 = 4,    // B arrives as 3 pre-split bf16 planes, 2 x 2 wave grid
+  FM_ABL_NOSPLIT = 5,    // MPIT_F32_ABLATE timing ablations (wrong products): no split,
+  FM_ABL_SPLITA = 6,     //   A split and B raw,
+  FM_ABL_SPLITB = 7,     //   A raw and B split
+  FM_BPLANES = 9,        // pre-split B, 4 x 1 wave grid (each wave splits its own A rows once)
+  FM_BPLANES_ACC1 = 10,  // FM_BPLANES with one accumulator and fragment prefetch (experiment)
+  FM_F16X3 = 11,         // fp16x3: B as 2 scaled fp16 planes (gemm_nt); split per use (gemm_tn)
+  FM_F16X3_ONCE = 12,    // gemm_tn fp16x3: operands split once per element into fp16 planes in LDS
+  FM_F16_PLANES = 13,    // fp16x3 with A and B (gemm_tn: Y and X) arriving as fp16 planes
+};
+constexpr bool fm_f16(int fm) { return fm == FM_F16X3 || fm == FM_F16X3_ONCE || fm == FM_F16_PLANES; }
+constexpr bool fm_ablate(int fm) { return fm == FM_ABL_NOSPLIT || fm == FM_ABL_SPLITA || fm == FM_ABL_SPLITB; }
+// gemm_nt: B arrives as planes / A arrives as planes / planes B has
+constexpr bool fm_b_planes(int fm) {
+  return fm == FM_BPLANES_W22 || fm == FM_BPLANES || fm == FM_BPLANES_ACC1 || fm == FM_F16X3 || fm == FM_F16_PLANES;
+}
+constexpr bool fm_a_planes(int fm) { return fm == FM_F16_PLANES; }
+constexpr int fm_b_nplanes(int fm) { return fm_f16(fm) ? 2 : 3; }
+// fp32 k-tiles are 32 deep (128-B LDS rows) in every mode but FM_NATIVE and FM_X6_K16
+constexpr bool fm_k32(int fm) { return fm != FM_NATIVE && fm != FM_X6_K16; }
+// built for 128-row tiles on a 2-deep ring only: the pre-split kernels and the ablations
+constexpr bool fm_ring2_only(int fm) { return fm_b_planes(fm) || fm_ablate(fm); }
+
 // column-reduction epilogue operands (see gemm_nt_kernel)
 struct EpiArgs {
   float* part;                 // [row0 + tiles][2][N] fp32 partials
@@ -337,8 +370,8 @@ __device__ __forceinline__ int swzk(int row, int chunk) {
 // (64 bf16: 16 MFMAs per wave between fragment refills, half the barriers per FLOP)
 // fp32 bf16x6 with FM = 3 stages 32-deep k-tiles (128-B rows of 32 floats: two k16 MFMA steps
 // per barrier) instead of FM = 1's 16-deep ones.
-__host__ __device__ constexpr int nt_bkb(int BM, int BN, int FM = 0) {
-  return (BM == 256 && BN == 256) || FM == 3 || FM == 4 || FM >= 5 ? 128 : 64;
+__host__ __device__ constexpr int nt_bkb(int BM, int BN, int FM = FM_NATIVE) {
+  return (BM == 256 && BN == 256) || fm_k32(FM) ? 128 : 64;
 }
 
 typedef __attribute__((address_space(3))) void lds_void;
@@ -399,6 +432,10 @@ constexpr bool kFm13W22 = true;
 #else
 constexpr bool kFm13W22 = false;
 #endif
+// gemm_nt wave grid over the block tile: 4 x 1 (each wave all the tile's columns) or 2 x 2
+constexpr bool fm_waves_4x1(int fm) {
+  return fm == FM_BPLANES || fm == FM_BPLANES_ACC1 || fm == FM_F16X3 || (fm == FM_F16_PLANES && !kFm13W22);
+}
 #ifdef MPIT_FM13_PF
 constexpr bool kFm13Pf = true;
 #else
@@ -768,8 +805,21 @@ __device__ __forceinline__ void stats_fold(const EpiArgs& ep, void* smem, int64_
 // the tile about to be used (a __syncthreads() would drain the whole ring). The LDS image
 // is lane-linear per wave instruction (16 rows x 64 B); the swizzle is applied on the
 // global source address.
-template <typename T, int BM, int BN, int STAGES, int EPI, bool CONV, int FM = 0>
-__global__ __launch_bounds__(256, sizeof(T) == 4 ? (BM == 256 ? (BN == 64 ? 2 : 1) : (BN == 64 ? 3 : 2)) : (BM == 256 ? (BN == 256 ? 1 : 2) : (STAGES == 2 ? (CONV || EPI == 3 ? 4 : 5) : 2))) void gemm_nt_kernel(const T* __restrict__ A, int64_t lda,
+// blocks per CU the register budget of gemm_nt_kernel is sized for
+constexpr int nt_occupancy(bool f32, int BM, int BN, int STAGES, int EPI, bool CONV) {
+  if (f32) return BM == 256 ? (BN == 64 ? 2 : 1) : (BN == 64 ? 3 : 2);
+  if (BM == 256) return BN == 256 ? 1 : 2;
+  if (STAGES != 2) return 2;
+  return CONV || EPI == EPI_BNRED2 ? 4 : 5;
+}
+static_assert(nt_occupancy(true, 256, 64, 2, EPI_NONE, false) == 2 && nt_occupancy(true, 256, 128, 3, EPI_NONE, true) == 1 &&
+              nt_occupancy(true, 128, 64, 4, EPI_STATS, true) == 3 && nt_occupancy(true, 128, 128, 2, EPI_BNRED2, false) == 2);
+static_assert(nt_occupancy(false, 256, 256, 2, EPI_NONE, false) == 1 && nt_occupancy(false, 256, 128, 3, EPI_NONE, true) == 2 &&
+              nt_occupancy(false, 128, 128, 2, EPI_STATS, true) == 4 && nt_occupancy(false, 128, 64, 2, EPI_BNRED2, false) == 4 &&
+              nt_occupancy(false, 128, 128, 2, EPI_BNRED, false) == 5 && nt_occupancy(false, 128, 64, 3, EPI_NONE, false) == 2 &&
+              nt_occupancy(false, 128, 128, 4, EPI_BNRED2, true) == 2);
+template <typename T, int BM, int BN, int STAGES, int EPI, bool CONV, int FM = FM_NATIVE>
+__global__ __launch_bounds__(256, nt_occupancy(sizeof(T) == 4, BM, BN, STAGES, EPI, CONV)) void gemm_nt_kernel(const T* __restrict__ A, int64_t lda,
                                                          const T* __restrict__ B, int64_t ldb,
                                                          T* C, int64_t ldc, int64_t M, int N, int K,
                                                          int ntn, EpiArgs ep, const T* Cin,
@@ -780,7 +830,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? (BM == 256 ? (BN == 64 ? 2 : 
   // wave grid over the tile: 2 x 2 (each wave 64 x 64 of a 128 x 128 tile), or for FM 9
   // (pre-split B) 4 x 1: each wave owns 32 rows x all 128 columns, so every A row is split in
   // registers by exactly one wave (the ready-made B planes are the shared operand)
-  constexpr int WGM = (sizeof(T) == 4 && (FM == 9 || FM == 10 || FM == 11 || (FM == 13 && !kFm13W22))) ? 4 : 2,
+  constexpr int WGM = (sizeof(T) == 4 && fm_waves_4x1(FM)) ? 4 : 2,
                 WGN = NW / WGM;
   constexpr int WM = BM / WGM, WN = BN / WGN;
   constexpr int TM = WM / 32, TN = WN / 32;
@@ -794,12 +844,12 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? (BM == 256 ? (BN == 64 ? 2 : 
   // 32 bf16 per row — the A operand alone is split in registers
   // FM 11 (fp32, fp16x3): B arrives as two fp16 planes (h, l) of the scaled weight, staged the
   // same way (two 64-B-row images); A is scaled and split in registers (split2h)
-  constexpr bool BSPLIT = F32 && (FM == 4 || FM == 9 || FM == 10 || FM == 11 || FM == 13);
-  constexpr int NPL = FM == 11 || FM == 13 ? 2 : 3;  // B planes
+  constexpr bool BSPLIT = F32 && fm_b_planes(FM);
+  constexpr int NPL = fm_b_nplanes(FM);  // B planes
   constexpr int IBP = BSPLIT ? BN / 16 / NW : 0;  // glds per wave per B plane (16 rows x 64 B)
   // FM 13: A arrives as two fp16 planes too (h, l of A * 2^ea; plane stride ep.aps), staged
   // like B's (two 64-B-row images of 32 halves per row): nothing is split in the kernel
-  constexpr bool ASPLIT = F32 && FM == 13;
+  constexpr bool ASPLIT = F32 && fm_a_planes(FM);
   constexpr int IAP = ASPLIT ? BM / 16 / NW : 0;  // glds per wave per A plane
   static_assert(!ASPLIT || (IAP >= 1 && kF11Buf), "FM 13 stages A planes through buffer descriptors");
   constexpr int NI = BSPLIT ? (ASPLIT ? 2 * IAP : IA) + NPL * IBP : IA + IB;
@@ -807,7 +857,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? (BM == 256 ? (BN == 64 ? 2 : 
   constexpr int BTILE = BSPLIT ? NPL * BN * 32 / 2 : BN * BK;
   constexpr int TILE = BM * BK + BTILE;
   static_assert(IA >= 1 && IB >= 1, "tile too small");
-  static_assert(!F32 || BKB == 64 || FM == 3 || FM == 4 || FM >= 5, "fp32 tiles stage 64-B rows (FM 3: 128-B)");
+  static_assert(!F32 || BKB == 64 || fm_k32(FM), "fp32 tiles stage 64-B rows (FM 3: 128-B)");
   extern __shared__ __attribute__((aligned(16))) uint16_t smem_raw[];
   T* smem = reinterpret_cast<T*>(smem_raw);
   const T* zline = reinterpret_cast<const T*>(g_zero_line);
@@ -864,7 +914,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? (BM == 256 ? (BN == 64 ? 2 : 
   // column row (of each plane) — and a tile's k offset moves the descriptor base (SALU), so
   // issuing a tile costs no per-lane 64-bit address arithmetic, no padding branches and no
   // readfirstlane of the LDS address. The host checks that every offset stays below 2^31.
-  constexpr bool F11B = (F32 && (FM == 11 || FM == 13) && kF11Buf) || (!F32 && FM == 0 && kBf16Buf);
+  constexpr bool F11B = (F32 && fm_f16(FM) && kF11Buf) || (!F32 && FM == FM_NATIVE && kBf16Buf);
   constexpr int NVB = BSPLIT ? IBP : IB;
   [[maybe_unused]] uint32_t voa[F11B ? NAR : 1], vob[F11B ? NVB : 1];
   constexpr int AES = ASPLIT ? 2 : int(sizeof(T));  // bytes per A element in global memory
@@ -1029,7 +1079,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? (BM == 256 ? (BN == 64 ? 2 : 
   // FM 11: operand scales 2^ea (A, applied in the split) and 2^eb (B, applied by the plan)
   [[maybe_unused]] int ea = 0, eb = 0;
   [[maybe_unused]] float sa = 1.f, sa11 = 2048.f;
-  if constexpr (F32 && (FM == 11 || FM == 13)) {
+  if constexpr (F32 && fm_f16(FM)) {
     ea = fp16_exp(ep.amax_a);
     eb = fp16_exp(ep.amax_b);
     sa = exp2i(ea);
@@ -1049,7 +1099,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? (BM == 256 ? (BN == 64 ? 2 : 
     if (kt + STAGES - 1 < nk) issue(kt + STAGES - 1, (kt + STAGES - 1) % STAGES);
     const T* As = smem + (kt % STAGES) * TILE;
     const T* Bs = As + BM * BK;
-    if constexpr (F32 && FM == 10) {
+    if constexpr (F32 && FM == FM_BPLANES_ACC1) {
       // FM 10 (experiment, MPIT_F32_NT=acc1): FM 9 with the six products accumulated in ONE
       // register set (standard fp32 accumulation instead of the separate small-term sum) and
       // the fragments of step kk + 1 read before the split + MFMAs of step kk (the 64
@@ -1099,7 +1149,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? (BM == 256 ? (BN == 64 ? 2 : 
           }
       }
       continue;
-    } else if constexpr (F32 && FM == 13) {
+    } else if constexpr (F32 && FM == FM_F16_PLANES) {
       // fp16x3 on planes: A's h, l read ready-made like B's (chunk 2kk + fh of a 64-B plane
       // row); hh -> acc, hl + lh -> tacc — FM 11's products on the same planes, no split
       const uint16_t* Bp = reinterpret_cast<const uint16_t*>(Bs);
@@ -1142,7 +1192,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? (BM == 256 ? (BN == 64 ? 2 : 
           }
       }
       continue;
-    } else if constexpr (F32 && FM == 11) {
+    } else if constexpr (F32 && FM == FM_F16X3) {
       // fp16x3: B planes h, l read ready-made; the lane's 8 A floats of k16 step kk (chunks
       // 4kk + 2fh, +1) scaled and split in registers; hh -> acc, hl + lh -> tacc
       const uint16_t* Bp = reinterpret_cast<const uint16_t*>(Bs);
@@ -1205,7 +1255,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? (BM == 256 ? (BN == 64 ? 2 : 
         mfma_x3<TM, TN>(acc, tacc, ah, am, al, bh, bm, bl, true);
       }
       continue;
-    } else if constexpr (F32 && FM >= 5 && FM <= 7) {
+    } else if constexpr (F32 && fm_ablate(FM)) {
       // TIMING ABLATION ONLY (MPIT_F32_ABLATE=nosplit): FM 3's loop with the operand split
       // replaced by a reinterpretation of the raw fp32 bits (wrong numbers, zero VALU) — how
       // fast the kernel would be if its operands arrived pre-split
@@ -1217,7 +1267,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? (BM == 256 ? (BN == 64 ? 2 : 
           const int r = wm * WM + i * 32 + fr;
           const float4 x0 = *reinterpret_cast<const float4*>(As + r * BK + swzk<BKB>(r, 4 * kk + 2 * fh) * 4);
           const float4 x1 = *reinterpret_cast<const float4*>(As + r * BK + swzk<BKB>(r, 4 * kk + 2 * fh + 1) * 4);
-          if constexpr (FM == 6) {  // ablation 6: A split, B raw
+          if constexpr (FM == FM_ABL_SPLITA) {  // ablation 6: A split, B raw
             const float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
             split3(v, ah[i], am[i], al[i]);
           } else {
@@ -1231,7 +1281,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? (BM == 256 ? (BN == 64 ? 2 : 
           const int r = wn * WN + j * 32 + fr;
           const float4 x0 = *reinterpret_cast<const float4*>(Bs + r * BK + swzk<BKB>(r, 4 * kk + 2 * fh) * 4);
           const float4 x1 = *reinterpret_cast<const float4*>(Bs + r * BK + swzk<BKB>(r, 4 * kk + 2 * fh + 1) * 4);
-          if constexpr (FM == 7) {  // ablation 7: A raw, B split
+          if constexpr (FM == FM_ABL_SPLITB) {  // ablation 7: A raw, B split
             const float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
             split3(v, bh[j], bm[j], bl[j]);
           } else {
@@ -1243,7 +1293,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? (BM == 256 ? (BN == 64 ? 2 : 
         mfma_x3<TM, TN>(acc, tacc, ah, am, al, bh, bm, bl, true);
       }
       continue;
-    } else if constexpr (F32 && (FM == 1 || FM == 3)) {
+    } else if constexpr (F32 && (FM == FM_X6_K16 || FM == FM_X6_K32)) {
       // bf16x6: the lane's 8 floats of a row in k16 step kk (chunks 4kk + 2fh, +1 of the row)
       // are exactly the k = 8fh + j operand of one v_mfma_f32_32x32x16_bf16; split each
       // fragment in registers
@@ -1372,7 +1422,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? (BM == 256 ? (BN == 64 ? 2 : 
     }
   }
 
-  if constexpr (F32 && (FM == 11 || FM == 13)) {  // (hh + 2^-11 (hl + lh)) 2^-(ea + eb), exact scalings
+  if constexpr (F32 && fm_f16(FM)) {  // (hh + 2^-11 (hl + lh)) 2^-(ea + eb), exact scalings
     const float ia = exp2i(-ea), ib = exp2i(-eb);
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -1380,7 +1430,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? (BM == 256 ? (BN == 64 ? 2 : 
       for (int j = 0; j < TN; ++j)
 #pragma unroll
         for (int v = 0; v < 16; ++v) acc[i][j][v] = fmaf(tacc[i][j][v], 1.f / 2048.f, acc[i][j][v]) * ia * ib;
-  } else if constexpr (F32 && FM != 0) {  // hh + the five small terms
+  } else if constexpr (F32 && FM != FM_NATIVE) {  // hh + the five small terms
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -1766,7 +1816,7 @@ __device__ __forceinline__ void tn_tile_sum(const float* src, int nsrc, int64_t 
   }
 }
 
-template <typename T, int TBN, int TBK, int STAGES, bool CONV, int FM = 0, int KR = kRows>
+template <typename T, int TBN, int TBK, int STAGES, bool CONV, int FM = FM_NATIVE, int KR = kRows>
 __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const T* __restrict__ Y, int64_t ldy,
                                                          const T* __restrict__ X, int64_t ldx,
                                                          float* __restrict__ part, int64_t M, int N, int K,
@@ -1782,7 +1832,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const T* __restrict__ Y
   constexpr int RY = 64 / CY, RX = 64 / CX;           // rows per glds wave-instruction
   constexpr int IY = kRows / RY / 4, IX = kRows / RX / 4;  // glds per wave per tile
   // FM 13: 16-bit staging of TWO planes (h, l) per operand: images YH, YL, XH, XL
-  constexpr bool P13 = FM == 13;
+  constexpr bool P13 = FM == FM_F16_PLANES;
   constexpr int NPLT = P13 ? 2 : 1;
   constexpr int NI = (IY + IX) * NPLT;
   constexpr int TILE = kRows * (TBN + TBK) * NPLT;
@@ -1971,7 +2021,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const T* __restrict__ Y
   f32x16 lacc[LACC ? TM : 1][LACC ? TN : 1];
   [[maybe_unused]] int ey = 0, ex = 0;
   [[maybe_unused]] float sy = 1.f, sy11 = 2048.f, sx = 1.f, sx11 = 2048.f;
-  if constexpr ((F32 && (FM == 11 || FM == 12)) || P13) {
+  if constexpr ((F32 && fm_f16(FM)) || P13) {
     ey = fp16_exp(red.amax_y);
     ex = fp16_exp(red.amax_x);
     sy = exp2i(ey);
@@ -2009,7 +2059,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const T* __restrict__ Y
       __syncthreads();
     }
     if (st + STAGES - 1 < nsteps) issue(st + STAGES - 1, int((st + STAGES - 1) % STAGES));
-    if constexpr (F32 && FM == 1) {
+    if constexpr (F32 && FM == FM_X6_K16) {
       // bf16x6 (see split3): lane (fr, fh) of a 16-row step holds Y[16kk + 8fh + j][n0' + fr]
       // and X[16kk + 8fh + j][k0' + fr], j = 0..7 — the k = 8fh + j operands of one
       // v_mfma_f32_32x32x16_bf16, read down a column (ds_read_b32, 32 consecutive floats
@@ -2034,7 +2084,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const T* __restrict__ Y
         }
         mfma_x3<TM, TN>(acc, lacc, ah, am, al, bh, bm, bl, false);
       }
-    } else if constexpr (F32 && FM == 11) {
+    } else if constexpr (F32 && FM == FM_F16X3) {
       // fp16x3 (see split2h): the same column reads, each operand scaled and split into fp16
       // h, l; hh -> acc, hl + lh -> lacc
 #pragma unroll
@@ -2064,7 +2114,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const T* __restrict__ Y
             lacc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], lacc[i][j], 0, 0, 0);
           }
       }
-    } else if constexpr (F32 && FM == 12) {
+    } else if constexpr (F32 && FM == FM_F16X3_ONCE) {
       // fp16x3, split ONCE per element (FM 11 splits every element in each of the two waves
       // that read it, after 8 ds_read_b32 column reads per fragment): every thread takes its
       // share of this stage's fp32 rows (row-contiguous float4), the block barriers, and the
@@ -2244,12 +2294,12 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const T* __restrict__ Y
     }
     }
   }
-  if constexpr (F32 && FM == 1) {
+  if constexpr (F32 && FM == FM_X6_K16) {
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
       for (int j = 0; j < TN; ++j) acc[i][j] += lacc[i][j];
-  } else if constexpr ((F32 && (FM == 11 || FM == 12)) || P13) {
+  } else if constexpr ((F32 && fm_f16(FM)) || P13) {
     const float iy = exp2i(-ey), ix = exp2i(-ex);
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -2819,25 +2869,11 @@ int64_t gemm_nt_tiles(int64_t M) { return (M + 127) / 128; }
 
 int64_t gemm_nt_fold_lvl_floats(int N) { return int64_t(kFoldMaxGroups) * 3 * N; }
 
-// Block tile of gemm_nt: 0 = 128 x (128 | 64), 1 = 256 x 128, 2 = 256 x 256;
-// MPIT_GEMM_TILE=128|256x128|256 selects one (A/B runs, large plain GEMMs). fp32 runs the
-// 128-row tiles only (its MFMA is 16x slower per FLOP: LDS-bound tile shapes do not matter).
-static int nt_tile_config(int64_t M, int N, int K, bool conv, int cin_conv, bool f32) {
-  static const int forced = [] {
-    const char* e = std::getenv("MPIT_GEMM_TILE");
-    if (!e) return -1;
-    const std::string v(e);
-    return v == "256" ? 2 : v == "256x128" ? 1 : v == "128" ? 0 : -1;
-  }();
-  if (f32) {
-    // MPIT_F32_TILE=256x128: 256 x 128 blocks (1 per CU, 128 x 64 per wave) for the bf16x6
-    // fp32 GEMMs, whose 6 MFMAs per product make them compute-bound
-    static const int f32_forced = [] {
-      const char* e = std::getenv("MPIT_F32_TILE");
-      return e && std::string(e) == "256x128" ? 1 : 0;
-    }();
-    return f32_forced == 1 && N % 128 == 0 ? 1 : 0;
-  }
+// Every environment knob of the GEMM launchers, read once on first use (gemm_knobs()). Each is
+// an A/B switch; the measurement that justified its default is quoted beside it.
+struct GemmKnobs {
+  // MPIT_GEMM_TILE=128|256x128|256: force the block tile of the 16-bit gemm_nt (-1: by shape;
+  // 0 = 128 x (128 | 64), 1 = 256 x 128, 2 = 256 x 256). A/B runs, large plain GEMMs.
   // Measured (profiles/gemm_big_tile_ab_r01.jsonl, gemm_bk64_128tile_ab_r01.jsonl): 256x256
   // (BK 64) beats 128x128 on large square GEMMs (8192^3: 944 vs 611 TFLOP/s) and 256x128 on
   // 50176x256x2304 (+18 %), yet inside the models all-256 tiles lose end to end (round 1:
@@ -2846,38 +2882,215 @@ static int nt_tile_config(int64_t M, int N, int K, bool conv, int cin_conv, bool
   // where K is deep (>= 1024) AND the grid still has >= 4 blocks per CU — VGG-16's 112/56-
   // pixel 3x3 convolutions and their backward-data, no ResNet-50 shape — VGG-16 bf16 EASGD
   // +3.5 % (4,944 vs 4,774 / 4,824 img/s with every GEMM on 256x128, gpurun_out/r04vgg).
-  // MPIT_GEMM_DEEPK=k: 256 x 128 for every GEMM with K >= k, whatever its grid (default 2304:
-  // VGG-16 bf16 5,319 vs 5,239 img/s, r05i; ResNet-50 bf16 within noise, r05d; 0 = off)
-  static const int deepk = [] {
-    const char* e = std::getenv("MPIT_GEMM_DEEPK");
-    return e ? std::atoi(e) : 2304;
-  }();
-  int cfg = forced >= 0 ? forced
-                        : (K >= 1024 && N % 128 == 0 && ((M + 255) / 256) * int64_t(N / 128) >= 1024 ? 1 : 0);
-  if (forced < 0 && deepk > 0 && K >= deepk && N % 128 == 0) cfg = 1;
-  if (cfg == 2 && (N % 256 || K % 64 || (conv && cin_conv % 64))) cfg = N % 128 ? 0 : 1;
+  int tile = env_is("MPIT_GEMM_TILE", "256") ? 2 : env_is("MPIT_GEMM_TILE", "256x128") ? 1
+             : env_is("MPIT_GEMM_TILE", "128") ? 0 : -1;
+  // MPIT_GEMM_DEEPK=k: 256 x 128 for every 16-bit GEMM with K >= k, whatever its grid (default
+  // 2304: VGG-16 bf16 5,319 vs 5,239 img/s, r05i; ResNet-50 bf16 within noise, r05d; 0 = off)
+  int deepk = env_int("MPIT_GEMM_DEEPK", 2304);
+  // MPIT_GEMM_STAGES caps gemm_nt's ring depth (A/B measurements). fp32: the 64 KB epilogue tile
+  // of a 128x128 block holds a 4-deep 16-deep ring (or a 2-deep 32-deep one) for free;
+  // MPIT_F32_STAGES sets the fp32 cap whatever N is (0: unset)
+  int max_stages = env_int("MPIT_GEMM_STAGES", 2, 2, 4);
+  int f32_stages = env_int("MPIT_F32_STAGES", 0, 2, 4);
+  // MPIT_F32_TILE=256x128: 256 x 128 blocks (1 per CU, 128 x 64 per wave) for the bf16x6 fp32
+  // GEMMs, whose 6 MFMAs per product make them compute-bound.
+  // MPIT_F32_TILE=256x64: the fp16x3 GEMMs with N == 64 on 256 x 64 blocks (each wave 64 x 64
+  // instead of 32 x 64: twice the MFMAs per barrier and per A fragment split, 2 blocks/CU)
+  bool f32_t256x128 = env_is("MPIT_F32_TILE", "256x128");
+  bool f32_t256x64 = env_is("MPIT_F32_TILE", "256x64");
+  // MPIT_F32_MFMA=native: fp32 GEMMs on the fp32-input MFMA (exact fmaf chains, 1/2.7 of the
+  // split path's peak) instead of the split products on the 16-bit MFMAs (default)
+  bool f32_split = !env_is("MPIT_F32_MFMA", "native");
+  // MPIT_F32_BK=16: bf16x6 on 16-deep k-tiles (FM_X6_K16) even where K and the conv's channels
+  // are multiples of 32. Same-box ResNet-50 fp32 bench: 32-deep 4075 vs 16-deep 4016 img/s
+  // (profiles/gemm_fp32_variants_ab_r02.md)
+  int f32_bk = env_int("MPIT_F32_BK", 32) == 16 ? 16 : 32;
+  // MPIT_F32_ABLATE=nosplit|splitA|splitB: timing ablations in place of FM_X6_K32 (0: none)
+  int ablate = env_is("MPIT_F32_ABLATE", "nosplit") ? FM_ABL_NOSPLIT : env_is("MPIT_F32_ABLATE", "splitA") ? FM_ABL_SPLITA
+               : env_is("MPIT_F32_ABLATE", "splitB") ? FM_ABL_SPLITB : 0;
+  // pre-split B planes. MPIT_F32_WAVES=2x2: the 2 x 2 wave grid (FM_BPLANES_W22) instead of
+  // 4 x 1 (FM_BPLANES); MPIT_F32_NT=acc1: FM_BPLANES_ACC1 (experiment)
+  bool w22 = env_is("MPIT_F32_WAVES", "2x2");
+  bool acc1 = env_is("MPIT_F32_NT", "acc1");
+  // MPIT_F32_BN64=1: fp32 GEMMs on 128x64 tiles (3 blocks per CU instead of 2) — A/B knob
+  bool f32_bn64 = env_is("MPIT_F32_BN64", "1");
+  // MPIT_GEMM_LOG=1: one stderr line per GEMM launch (kind, M, N, K, conv, epilogue / splits),
+  // in issue order — scripts/gemm_calls.py joins it with a kernel trace for per-call TFLOP/s
+  bool log = env_is("MPIT_GEMM_LOG", "1");
+
+  // MPIT_TN_OCC=1: one gemm_tn block per CU (its LDS request padded to kTnCapShm), so a CU
+  // running a backward-weight block of the side stream always has room for one block of the
+  // critical path's GEMMs (64 KiB) next to it; the split plan then targets one block per CU.
+  bool tn_cap1 = env_is("MPIT_TN_OCC", "1");
+  // MPIT_TN_SPLIT_MUL=k: k times the splits (shorter blocks that free their CU sooner for
+  // the critical path's kernels, at k times the partial-sum traffic) — A/B knob
+  // (MPIT_TN_SPLIT_DIV=k: 1/k of them — longer blocks, less partial-sum traffic)
+  int split_mul = env_int("MPIT_TN_SPLIT_MUL", 1, 1, 8);
+  int split_div = env_int("MPIT_TN_SPLIT_DIV", 1, 1, 8);
+  // MPIT_TN_MIN_ROWS=r raises the floor of 8 staged steps per block (fewer, longer splits
+  // where M is deep and the output small — less partial-sum traffic; A/B knob)
+  int64_t min_rows = std::max<int64_t>(8 * kRows, env_i64("MPIT_TN_MIN_ROWS", 8 * kRows));
+  // MPIT_TN_FUSED=1: the split reduction runs inside the GEMM (last block per tile / group).
+  // Bitwise equal to the split_reduce launches but slower on ResNet-50's wgrads (the tail sum
+  // of a tile is left to one block: profiles/tn_fused_reduction_ab_r02.md), so opt-in.
+  bool tn_fused = env_is("MPIT_TN_FUSED", "1");
+  // fp16x3 wgrad: FM_F16X3_ONCE (split once per element into fp16 planes in LDS, transposed
+  // fragment reads) unless MPIT_TN_F16S=0 (FM_F16X3: split per use after column reads)
+  bool f16s = !env_is("MPIT_TN_F16S", "0");
+  // MPIT_GEMM_TN_STAGES: ring depth of the 32-row bf16 ring (A/B measurements; 4 by default,
+  // <= 2: 2). fp32 stages twice the bytes per row and computes 16x longer per step: 2 stages.
+  int tn_stages = env_int("MPIT_GEMM_TN_STAGES", 4) <= 2 ? 2 : 4;
+  // fp32 128 x 128 tiles, MPIT_TN_F32S=1: the split-once kernel gemm_tn_f32s_kernel
+  // (experiment; bitwise equal, slower so far: profiles/wgrad_split_once_r03.md)
+  bool f32s = env_is("MPIT_TN_F32S", "1");
+  // bf16: 64-row staged steps on a 2-deep ring (MPIT_TN_KR_STAGES=3: 3-deep) — the LDS of a
+  // 4 x 32-row ring, half its barriers per row. Default since r05o: VGG-16 bf16 5,557 vs 5,480
+  // img/s, ResNet-50 bf16 11,674 vs 11,596 (r05d). MPIT_TN_KROWS=32: the 4 x 32-row ring (0)
+  int kr64_stages = env_int("MPIT_TN_KROWS", 64) == 32 ? 0 : (env_int("MPIT_TN_KR_STAGES", 2) == 3 ? 3 : 2);
+};
+static const GemmKnobs& gemm_knobs() {
+  static const GemmKnobs k;
+  return k;
+}
+
+// What a gemm_nt call is: the inputs its kernel choice depends on, and nothing else
+struct NtQuery {
+  bool f32;
+  int64_t M;
+  int N, K;
+  bool conv;           // implicit-GEMM convolution (ConvGeo given)
+  int C, pitch, ostr;  // ... and the ConvGeo fields that matter
+  int epi;
+  int64_t lda, ldb;
+  int64_t bps, aps;    // plane strides of B / A (0: not planes)
+  bool amax_a, amax_b;
+};
+// ... and what runs for it: gemm_nt_kernel<T, BM, BN, STAGES, EPI, CONV, FM>
+struct NtPlan {
+  int BM, BN, STAGES, EPI, CONV, FM;
+  int bk;       // k-tile depth (elements)
+  int64_t mtn;  // row tiles
+  int ntn;      // column tiles
+  int64_t grid;
+  size_t lds;   // dynamic LDS bytes
+};
+
+// Block tile of the bf16 gemm_nt: 0 = 128 x (128 | 64), 1 = 256 x 128, 2 = 256 x 256. fp32 runs
+// the 128-row tiles (its MFMA is 16x slower per FLOP: LDS-bound tile shapes do not matter)
+// unless MPIT_F32_TILE asks for 256 x 128.
+static int nt_tile_config(const NtQuery& q, const GemmKnobs& kn) {
+  const int N = q.N, K = q.K;
+  if (q.f32) return kn.f32_t256x128 && N % 128 == 0 ? 1 : 0;
+  int cfg = kn.tile >= 0 ? kn.tile
+                         : (K >= 1024 && N % 128 == 0 && ((q.M + 255) / 256) * int64_t(N / 128) >= 1024 ? 1 : 0);
+  if (kn.tile < 0 && kn.deepk > 0 && K >= kn.deepk && N % 128 == 0) cfg = 1;
+  if (cfg == 2 && (N % 256 || K % 64 || (q.conv && q.C % 64))) cfg = N % 128 ? 0 : 1;
   if (cfg == 1 && N % 128) cfg = 0;
   return cfg;
 }
 
-// fp32 GEMM mode: 1 = bf16x6 split products on the bf16 MFMA (default), 0 = the fp32-input
-// MFMA (exact fmaf chains, 1/2.7 of the split path's peak). MPIT_F32_MFMA=native selects 0.
-static int f32_mode() {
-  static const int m = [] {
-    const char* e = std::getenv("MPIT_F32_MFMA");
-    return e && std::string(e) == "native" ? 0 : 1;
-  }();
-  return m;
+// The kernel instantiation, grid and LDS of a gemm_nt call. Pure: no HIP state, no pointers
+// (the launcher checks alignment and spans). Throws for operand combinations no kernel takes.
+static NtPlan nt_plan(const NtQuery& q, const GemmKnobs& kn) {
+  const int N = q.N, K = q.K;
+  if (q.epi == EPI_BNRED2 && q.conv) throw std::invalid_argument("gemm_nt: paired BN reduction is for 1x1 GEMMs");
+  if (q.epi == EPI_RELUB && (!q.conv || q.ostr != 1))
+    throw std::invalid_argument("gemm_nt: the fused ReLU epilogue is for stride-1 convolutions");
+  // fp32: bf16x6 on 32-deep k-tiles where K and the conv's channels are multiples of 32 (a
+  // row-tap stem only with ready-made B planes), else on 16-deep ones
+  int fm = !q.f32 || !kn.f32_split ? FM_NATIVE
+           : (kn.f32_bk == 32 && K % 32 == 0 && (!q.conv || (q.C % 32 == 0 && (!q.pitch || q.bps > 0))) ? FM_X6_K32
+                                                                                                      : FM_X6_K16);
+  if (fm == FM_X6_K32 && kn.ablate) fm = kn.ablate;
+  if (q.bps > 0) {  // B is pre-split planes: three bf16 ones, or with amax_b two fp16 ones (fp16x3)
+    if (fm != FM_X6_K32 || q.bps < int64_t(N) * q.ldb || q.ldb % 8)
+      throw std::invalid_argument("gemm_nt: pre-split B planes need the fp32 bf16x6 path with K % 32 == 0 "
+                                  "(and conv channels % 32 == 0), ldb % 8 == 0 and a plane stride >= N * ldb");
+    if (N % 64) throw std::invalid_argument("gemm_nt: pre-split B planes need N % 64 == 0");
+    fm = kn.w22 ? FM_BPLANES_W22 : (kn.acc1 ? FM_BPLANES_ACC1 : FM_BPLANES);
+    if (q.amax_b) {  // A needs its bound too
+      if (!q.amax_a) throw std::invalid_argument("gemm_nt: fp16 B planes need the A operand's amax bound");
+      fm = FM_F16X3;
+      if (q.aps > 0) {  // A as fp16 planes too
+        if (!kF11Buf || q.lda % 8 || (q.conv && q.pitch)) throw std::invalid_argument("gemm_nt: bad A planes");
+        fm = FM_F16_PLANES;
+      }
+    }
+  } else if (q.amax_b) {
+    throw std::invalid_argument("gemm_nt: amax_b is the scale of fp16 B planes (bps > 0)");
+  }
+  if (q.aps > 0 && fm != FM_F16_PLANES) throw std::invalid_argument("gemm_nt: A planes need fp16 B planes (fp16x3)");
+
+  NtPlan p{};
+  p.EPI = q.epi;
+  p.CONV = q.conv ? 1 : 0;
+  p.FM = fm;
+  const int nk = K / (fm_k32(fm) ? 32 : (q.f32 ? 16 : 32));
+  int cap = q.f32 && N % 128 == 0 ? (fm_k32(fm) ? 2 : 4) : kn.max_stages;
+  if (q.f32 && kn.f32_stages) cap = kn.f32_stages;
+  const int stages = fm_ring2_only(fm) ? 2 : std::min(cap, nk >= 4 ? 4 : (nk == 3 ? 3 : 2));
+  const int tcfg = fm_b_planes(fm) ? 0 : nt_tile_config(q, kn);
+  if (q.f32 && fm == FM_F16X3 && N == 64 && kn.f32_t256x64) {  // (FM_F16_PLANES runs 128-row tiles)
+    p.BM = 256, p.BN = 64, p.STAGES = 2;
+  } else if (tcfg == 1) {
+    p.BM = 256, p.BN = 128, p.STAGES = 3;
+  } else if (tcfg == 2) {
+    p.BM = 256, p.BN = 256, p.STAGES = 2;  // 2 x 64-deep stages = the 128 KB epilogue tile
+  } else {
+    p.BM = 128, p.BN = N % 128 == 0 && !(q.f32 && kn.f32_bn64) ? 128 : 64, p.STAGES = stages;
+  }
+  if (fm_ring2_only(fm) && !(p.BM == 256 && p.BN == 64) && !(p.BM == 128 && p.STAGES == 2))
+    throw std::logic_error("gemm_nt: pre-split kernels run 128-row tiles on a 2-deep ring");
+  const int bkb = nt_bkb(p.BM, p.BN, fm), esz = q.f32 ? 4 : 2;
+  p.bk = bkb / esz;
+  p.mtn = (q.M + p.BM - 1) / p.BM;
+  p.ntn = N / p.BN;
+  p.grid = p.mtn * p.ntn;
+  if (p.grid > INT32_MAX) throw std::invalid_argument("gemm_nt: too many tiles");
+  // LDS: the k-tile ring, reused by the epilogue's output tile and reduction table
+  const size_t brow = fm_b_planes(fm) ? size_t(64) * fm_b_nplanes(fm) : size_t(bkb);
+  p.lds = std::max({size_t(p.STAGES) * (size_t(p.BM) * bkb + size_t(p.BN) * brow), size_t(p.BM) * p.BN * esz,
+                    size_t(256) * 8 * 3 * sizeof(float)});
+  return p;
 }
 
-// MPIT_GEMM_LOG=1: one stderr line per GEMM launch (kind, M, N, K, conv, epilogue / splits),
-// in issue order — scripts/gemm_calls.py joins it with a kernel trace for per-call TFLOP/s
-static bool gemm_log() {
-  static const bool on = [] {
-    const char* e = std::getenv("MPIT_GEMM_LOG");
-    return e && std::string(e) == "1";
-  }();
-  return on;
+// f(integral_constant...) for the constants equal to the runtime values v[0], v[1], ...: one
+// IntList of candidates per value. False when a value is in no list or f itself says false.
+template <int... V>
+struct IntList {};
+template <class F, class... C>
+bool dispatch(const int*, std::tuple<>, F& f, C... c) {
+  return f(c...);
+}
+template <class F, int... V, class... L, class... C>
+bool dispatch(const int* v, std::tuple<IntList<V...>, L...>, F& f, C... c) {
+  return ((*v == V && dispatch(v + 1, std::tuple<L...>{}, f, c..., std::integral_constant<int, V>{})) || ...);
+}
+// every (f32, values...) of the lists that `built` admits, for the selection-table test
+template <class B, class... C>
+void enumerate(std::vector<std::vector<int>>& out, B built, std::tuple<>, C... c) {
+  if (built(c...)) out.push_back({c...});
+}
+template <class B, int... V, class... L, class... C>
+void enumerate(std::vector<std::vector<int>>& out, B built, std::tuple<IntList<V...>, L...>, C... c) {
+  (enumerate(out, built, std::tuple<L...>{}, c..., V), ...);
+}
+
+// The gemm_nt_kernel instantiations that are built, per element type: nothing else is ever
+// compiled, and the dispatcher refuses a plan outside this set.
+using NtLists = std::tuple<IntList<128, 256>, IntList<64, 128, 256>, IntList<2, 3, 4>,
+                           IntList<EPI_NONE, EPI_STATS, EPI_BNRED, EPI_BNRED2, EPI_RELUB>, IntList<0, 1>,
+                           IntList<FM_NATIVE, FM_X6_K16, FM_X6_K32, FM_BPLANES_W22, FM_ABL_NOSPLIT, FM_ABL_SPLITA,
+                                   FM_ABL_SPLITB, FM_BPLANES, FM_BPLANES_ACC1, FM_F16X3, FM_F16_PLANES>>;
+constexpr bool nt_built(bool f32, int BM, int BN, int ST, int EPI, int CONV, int FM) {
+  const bool t128 = BM == 128 && (BN == 128 || BN == 64);                        // any ring depth
+  const bool t256 = BM == 256 && ((BN == 128 && ST == 3) || (BN == (f32 ? 64 : 256) && ST == 2));
+  if (!t128 && !t256) return false;
+  if ((EPI == EPI_BNRED2 && CONV) || (EPI == EPI_RELUB && !CONV)) return false;  // 1x1 only / conv only
+  if (!f32) return FM == FM_NATIVE;
+  if (BM == 256 && BN == 64) return FM == FM_F16X3;  // MPIT_F32_TILE=256x64
+  if (fm_ring2_only(FM)) return BM == 128 && ST == 2;
+  return FM == FM_NATIVE || FM == FM_X6_K16 || FM == FM_X6_K32;
 }
 
 // group size (M-tiles) and ticket set of a folded BN finalize: <= kFoldMaxGroups groups of
@@ -2929,17 +3142,20 @@ static void fold_plan(EpiArgs& ep, int dev, hipStream_t s, int64_t mtn, int ntn)
   }
 }
 
-template <typename T>
-static void launch_nt_t(int dev, hipStream_t s, int64_t M, int N, int K, uintptr_t A, int64_t lda, uintptr_t B,
-                        int64_t ldb, uintptr_t C, int64_t ldc, uintptr_t cin, uintptr_t cmask, const ConvGeo* geo,
-                        const EpiArgs& ep_in, int epi, uintptr_t bias, bool relu, int64_t bps) {
-  constexpr bool F32 = sizeof(T) == 4;
-  EpiArgs ep = ep_in;  // the fold's group size and ticket set are filled in per launch
-  constexpr int EPC = epc<T>();
-  if (!gemm_nt_supported(M, N, K, F32))
-    throw std::invalid_argument(std::string("gemm_nt: need N % 64 == 0 and K % ") + (F32 ? "16" : "32") +
+static void nt_check_shape(int64_t M, int N, int K, bool f32) {
+  if (!gemm_nt_supported(M, N, K, f32))
+    throw std::invalid_argument(std::string("gemm_nt: need N % 64 == 0 and K % ") + (f32 ? "16" : "32") +
                                 " == 0 (M=" + std::to_string(M) + " N=" + std::to_string(N) + " K=" + std::to_string(K) +
                                 ")");
+}
+
+// bps > 0: B is pre-split planes of plane stride bps elements (fp32 only; see nt_plan)
+static void launch_nt(int dev, hipStream_t s, int64_t M, int N, int K, uintptr_t A, int64_t lda, uintptr_t B,
+                      int64_t ldb, uintptr_t C, int64_t ldc, uintptr_t cin, uintptr_t cmask, const ConvGeo* geo,
+                      const EpiArgs& ep_in, int epi, bool f32, uintptr_t bias = 0, bool relu = false, int64_t bps = 0) {
+  EpiArgs ep = ep_in;  // the fold's group size and ticket set are filled in per launch
+  const int EPC = f32 ? epc<float>() : epc<uint16_t>();
+  nt_check_shape(M, N, K, f32);
   check_ptr(A, "A");
   check_ptr(B, "B");
   check_ptr(C, "C");
@@ -2947,13 +3163,11 @@ static void launch_nt_t(int dev, hipStream_t s, int64_t M, int N, int K, uintptr
     throw std::invalid_argument("gemm_nt: bad leading dimensions");
   if (epi != EPI_NONE) {
     if (!ep.part) throw std::invalid_argument("gemm_nt: reduction epilogue needs a partials buffer");
-    if (epi == EPI_BNRED2 && geo) throw std::invalid_argument("gemm_nt: paired BN reduction is for 1x1 GEMMs");
     if (ep.fcoef && (epi != EPI_BNRED || ep.row0 != 0 || !ep.frstd || !ep.flvl))
       throw std::invalid_argument("gemm_nt: the BN finalize fold needs a single-launch EPI_BNRED with rstd and lvl");
     if (ep.scoef && (epi != EPI_STATS || ep.row0 != 0 || !ep.smean || !ep.srstd || !ep.flvl))
       throw std::invalid_argument("gemm_nt: the BN forward fold needs a single-launch EPI_STATS with mean, rstd and lvl");
     if (epi == EPI_RELUB) {
-      if (!geo || geo->ostr != 1) throw std::invalid_argument("gemm_nt: the fused ReLU epilogue is for stride-1 convolutions");
       if (!ep.x || ldc != N) throw std::invalid_argument("gemm_nt: the fused ReLU epilogue needs x and ldc == N");
       check_ptr(reinterpret_cast<uintptr_t>(ep.x), "ReLU y");
     }
@@ -2964,70 +3178,21 @@ static void launch_nt_t(int dev, hipStream_t s, int64_t M, int N, int K, uintptr
     }
   }
   hip_check(hipSetDevice(dev), "hipSetDevice");
-  if (gemm_log())
+  if (gemm_knobs().log)
     std::fprintf(stderr, "MPIT_GEMM nt %lld %d %d conv=%d epi=%d f32=%d\n", (long long)M, N, K, geo ? 1 : 0, epi,
-                 F32 ? 1 : 0);
-  const auto* a = reinterpret_cast<const T*>(A);
-  const auto* b = reinterpret_cast<const T*>(B);
-  auto* c = reinterpret_cast<T*>(C);
-  const auto* ci = reinterpret_cast<const T*>(cin);
+                 f32 ? 1 : 0);
   if (cin) check_ptr(cin, "Cin");
   if (cmask && (!cin || ldc != N)) throw std::invalid_argument("gemm_nt: cmask needs cin with ldc == N");
-  const auto* cm = reinterpret_cast<const uint8_t*>(cmask);
   if (bias) check_ptr(bias, "bias");
-  const auto* bs = reinterpret_cast<const float*>(bias);
-  const int rl = relu ? 1 : 0;
-  const ConvGeo g = geo ? *geo : ConvGeo{};
-  // fp32 variant: 0 native fp32 MFMA, 1 bf16x6 on 16-deep k-tiles, 3 bf16x6 on 32-deep ones
-  // (default where K and the conv's channels are multiples of 32; MPIT_F32_BK=16 forces 1).
-  // Same-box ResNet-50 fp32 bench: 32-deep 4075 vs 16-deep 4016 img/s (profiles/gemm_fp32_variants_ab_r02.md)
-  static const int f32_bk = [] {
-    const char* e = std::getenv("MPIT_F32_BK");
-    return e && std::atoi(e) == 16 ? 16 : 32;
-  }();
-  static const int ablate = [] {
-    const char* e = std::getenv("MPIT_F32_ABLATE");
-    if (!e) return 0;
-    const std::string v(e);
-    return v == "nosplit" ? 5 : v == "splitA" ? 6 : v == "splitB" ? 7 : 0;
-  }();
-  int fm = !F32 || f32_mode() != 1 ? 0
-           : (f32_bk == 32 && K % 32 == 0 && (!geo || (geo->C % 32 == 0 && (!geo->pitch || bps > 0))) ? 3 : 1);
-  if (fm == 3 && ablate) fm = ablate;
-  if (bps > 0) {  // B is three pre-split bf16 planes: only the FM 4 kernels read that
-    if (!F32 || fm != 3 || ablate || bps < int64_t(N) * ldb || ldb % 8)
-      throw std::invalid_argument("gemm_nt: pre-split B planes need the fp32 bf16x6 path with K % 32 == 0 "
-                                  "(and conv channels % 32 == 0), ldb % 8 == 0 and a plane stride >= N * ldb");
-    check_ptr(B + uintptr_t(bps) * 2, "B plane 1");
-    if (N % 64) throw std::invalid_argument("gemm_nt: pre-split B planes need N % 64 == 0");
-    // MPIT_F32_WAVES=2x2: the 2 x 2 wave grid (FM 4); default 4 x 1 (FM 9);
-    // MPIT_F32_NT=acc1: FM 10 (one accumulator, fragment prefetch; experiment)
-    static const bool w22 = [] {
-      const char* e = std::getenv("MPIT_F32_WAVES");
-      return e && std::string(e) == "2x2";
-    }();
-    static const bool acc1 = [] {
-      const char* e = std::getenv("MPIT_F32_NT");
-      return e && std::string(e) == "acc1";
-    }();
-    fm = w22 ? 4 : (acc1 ? 10 : 9);
-    if (ep.amax_b) {  // fp16 planes h, l of the scaled weight (fp16x3): A needs its bound too
-      if (!ep.amax_a) throw std::invalid_argument("gemm_nt: fp16 B planes need the A operand's amax bound");
-      check_ptr(B + uintptr_t(bps) * 2, "B plane 1");
-      fm = 11;
-      if (ep.aps > 0) {  // A as fp16 planes too (FM 13)
-        if (!kF11Buf || lda % 8 || (geo && geo->pitch)) throw std::invalid_argument("gemm_nt: bad A planes");
-        check_ptr(A + uintptr_t(ep.aps) * 2, "A plane 1");
-        fm = 13;
-      }
-    }
-  } else if (ep.amax_b) {
-    throw std::invalid_argument("gemm_nt: amax_b is the scale of fp16 B planes (bps > 0)");
-  }
-  if (ep.aps > 0 && fm != 13) throw std::invalid_argument("gemm_nt: A planes need fp16 B planes (fp16x3)");
-  if ((F32 && (fm == 11 || fm == 13) && kF11Buf) || (!F32 && kBf16Buf)) {
+  const NtPlan p = nt_plan(NtQuery{f32, M, N, K, geo != nullptr, geo ? geo->C : 0, geo ? geo->pitch : 0,
+                                   geo ? geo->ostr : 1, epi, lda, ldb, bps, ep.aps, ep.amax_a != nullptr,
+                                   ep.amax_b != nullptr},
+                           gemm_knobs());
+  if (fm_b_planes(p.FM)) check_ptr(B + uintptr_t(bps) * 2, "B plane 1");
+  if (fm_a_planes(p.FM)) check_ptr(A + uintptr_t(ep.aps) * 2, "A plane 1");
+  if ((f32 && fm_f16(p.FM) && kF11Buf) || (!f32 && kBf16Buf)) {
     // the buffer-descriptor staging keeps every lane offset below 2^31 bytes of its block base
-    const int64_t lim = int64_t(1) << 31, esz = fm == 13 ? 2 : int64_t(sizeof(T));
+    const int64_t lim = int64_t(1) << 31, esz = fm_a_planes(p.FM) ? 2 : (f32 ? 4 : 2);
     int64_t aspan;
     if (geo) {
       const int64_t hw = int64_t(geo->Ho) * geo->Wo;
@@ -3039,187 +3204,34 @@ static void launch_nt_t(int dev, hipStream_t s, int64_t M, int N, int K, uintptr
     if (aspan >= lim || (int64_t(256) * ldb + K) * esz >= lim)
       throw std::invalid_argument("gemm_nt: operand rows (or images) span >= 2 GiB per block");
   }
-  const int nk = K / (fm >= 3 ? 32 : nt_bk_of<T>());
-  // MPIT_GEMM_STAGES caps the ring depth (A/B measurements). fp32: the 64 KB epilogue tile
-  // of a 128x128 block holds a 4-deep 16-deep ring (or a 2-deep 32-deep one) for free.
-  static const int max_stages = [] {
-    const char* e = std::getenv("MPIT_GEMM_STAGES");
-    return e ? std::max(2, std::min(4, std::atoi(e))) : 2;
-  }();
-  static const int f32_stages = [] {
-    const char* e = std::getenv("MPIT_F32_STAGES");
-    return e ? std::max(2, std::min(4, std::atoi(e))) : 0;
-  }();
-  int cap = F32 && N % 128 == 0 ? (fm >= 3 ? 2 : 4) : max_stages;
-  if (F32 && f32_stages) cap = f32_stages;
-  // (the pre-split kernels, FM >= 4, are built for the 2-deep ring of 128-row tiles only)
-  const int stages = fm >= 4 ? 2 : std::min(cap, nk >= 4 ? 4 : (nk == 3 ? 3 : 2));
-  // (kernel templates are named at a non-template call site so their host stubs are emitted)
-#define MPIT_NT_OPT_IN(BM, BN, ST, EPI, CONV, FMV)                                                                 \
-  do {                                                                                                             \
-    static const bool opted = (hip_check(hipFuncSetAttribute(reinterpret_cast<const void*>(                       \
-                                                             &gemm_nt_kernel<T, BM, BN, ST, EPI, CONV, FMV>),     \
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, int(shm)),    \
-                                     "hipFuncSetAttribute"),                                                       \
-                               true);                                                                              \
-    (void)opted;                                                                                                   \
-  } while (0)
-#define MPIT_NT_LAUNCH1(BM, BN, ST, EPI, CONV)                                                                       \
-  do {                                                                                                             \
-    if constexpr (F32 && BM == 256 && BN == 64) { /* fp16x3 only (MPIT_F32_TILE=256x64) */                      \
-      if (fm != 11) throw std::logic_error("gemm_nt: 256 x 64 fp32 tiles are for the fp16x3 kernels (FM 11)");    \
-      MPIT_NT_OPT_IN(BM, BN, ST, EPI, CONV, 11);                                                                   \
-      hipLaunchKernelGGL((gemm_nt_kernel<T, BM, BN, ST, EPI, CONV, 11>), dim3(unsigned(nb)), dim3(256), shm, s, a,   \
-                         lda, b, ldb, c, ldc, M, N, K, ntn, ep, ci, cm, bs, rl, g, bps);                            \
-      break;                                                                                                       \
-    } else {                                                                                                       \
-    if constexpr (F32 && BM == 128 && ST == 2) {                                                                 \
-      if (fm == 13) {                                                                                              \
-        if (shm > 65536) MPIT_NT_OPT_IN(BM, BN, ST, EPI, CONV, 13);                                                 \
-        hipLaunchKernelGGL((gemm_nt_kernel<T, BM, BN, ST, EPI, CONV, 13>), dim3(unsigned(nb)), dim3(256), shm, s, a, \
-                           lda, b, ldb, c, ldc, M, N, K, ntn, ep, ci, cm, bs, rl, g, bps);                          \
-        break;                                                                                                     \
-      }                                                                                                            \
-      if (fm == 11) {                                                                                              \
-        if (shm > 65536) MPIT_NT_OPT_IN(BM, BN, ST, EPI, CONV, 11);                                                 \
-        hipLaunchKernelGGL((gemm_nt_kernel<T, BM, BN, ST, EPI, CONV, 11>), dim3(unsigned(nb)), dim3(256), shm, s, a, \
-                           lda, b, ldb, c, ldc, M, N, K, ntn, ep, ci, cm, bs, rl, g, bps);                          \
-        break;                                                                                                     \
-      }                                                                                                            \
-      if (fm >= 5 && fm <= 7) { /* timing ablations (MPIT_F32_ABLATE) */                                        \
-        if (fm == 5) {                                                                                             \
-          if (shm > 65536) MPIT_NT_OPT_IN(BM, BN, ST, EPI, CONV, 5);                                                \
-          hipLaunchKernelGGL((gemm_nt_kernel<T, BM, BN, ST, EPI, CONV, 5>), dim3(unsigned(nb)), dim3(256), shm, s, \
-                             a, lda, b, ldb, c, ldc, M, N, K, ntn, ep, ci, cm, bs, rl, g, bps);                          \
-        } else if (fm == 6) {                                                                                      \
-          if (shm > 65536) MPIT_NT_OPT_IN(BM, BN, ST, EPI, CONV, 6);                                                \
-          hipLaunchKernelGGL((gemm_nt_kernel<T, BM, BN, ST, EPI, CONV, 6>), dim3(unsigned(nb)), dim3(256), shm, s, \
-                             a, lda, b, ldb, c, ldc, M, N, K, ntn, ep, ci, cm, bs, rl, g, bps);                          \
-        } else {                                                                                                   \
-          if (shm > 65536) MPIT_NT_OPT_IN(BM, BN, ST, EPI, CONV, 7);                                                \
-          hipLaunchKernelGGL((gemm_nt_kernel<T, BM, BN, ST, EPI, CONV, 7>), dim3(unsigned(nb)), dim3(256), shm, s, \
-                             a, lda, b, ldb, c, ldc, M, N, K, ntn, ep, ci, cm, bs, rl, g, bps);                          \
-        }                                                                                                          \
-        break;                                                                                                     \
-      }                                                                                                            \
-      if (fm == 4) {                                                                                               \
-        if (shm > 65536) MPIT_NT_OPT_IN(BM, BN, ST, EPI, CONV, 4);                                                  \
-        hipLaunchKernelGGL((gemm_nt_kernel<T, BM, BN, ST, EPI, CONV, 4>), dim3(unsigned(nb)), dim3(256), shm, s, a, \
-                           lda, b, ldb, c, ldc, M, N, K, ntn, ep, ci, cm, bs, rl, g, bps);                          \
-        break;                                                                                                     \
-      }                                                                                                            \
-      if (fm == 9) {                                                                                               \
-        if (shm > 65536) MPIT_NT_OPT_IN(BM, BN, ST, EPI, CONV, 9);                                                  \
-        hipLaunchKernelGGL((gemm_nt_kernel<T, BM, BN, ST, EPI, CONV, 9>), dim3(unsigned(nb)), dim3(256), shm, s, a, \
-                           lda, b, ldb, c, ldc, M, N, K, ntn, ep, ci, cm, bs, rl, g, bps);                          \
-        break;                                                                                                     \
-      }                                                                                                            \
-      if (fm == 10) {                                                                                              \
-        if (shm > 65536) MPIT_NT_OPT_IN(BM, BN, ST, EPI, CONV, 10);                                                 \
-        hipLaunchKernelGGL((gemm_nt_kernel<T, BM, BN, ST, EPI, CONV, 10>), dim3(unsigned(nb)), dim3(256), shm, s, a, \
-                           lda, b, ldb, c, ldc, M, N, K, ntn, ep, ci, cm, bs, rl, g, bps);                          \
-        break;                                                                                                     \
-      }                                                                                                            \
-    }                                                                                                              \
-    if constexpr (F32) {                                                                                           \
-      if (fm >= 4) throw std::logic_error("gemm_nt: pre-split kernels run 128-row tiles on a 2-deep ring");        \
-      if (fm == 3) {                                                                                               \
-        if (shm > 65536) MPIT_NT_OPT_IN(BM, BN, ST, EPI, CONV, 3);                                                  \
-        hipLaunchKernelGGL((gemm_nt_kernel<T, BM, BN, ST, EPI, CONV, 3>), dim3(unsigned(nb)), dim3(256), shm, s, a, \
-                           lda, b, ldb, c, ldc, M, N, K, ntn, ep, ci, cm, bs, rl, g, bps);                               \
-        break;                                                                                                     \
-      }                                                                                                            \
-      if (fm == 1) {                                                                                               \
-        if (shm > 65536) MPIT_NT_OPT_IN(BM, BN, ST, EPI, CONV, 1);                                                  \
-        hipLaunchKernelGGL((gemm_nt_kernel<T, BM, BN, ST, EPI, CONV, 1>), dim3(unsigned(nb)), dim3(256), shm, s, a, \
-                           lda, b, ldb, c, ldc, M, N, K, ntn, ep, ci, cm, bs, rl, g, bps);                               \
-        break;                                                                                                     \
-      }                                                                                                            \
-    }                                                                                                              \
-    if (shm > 65536) MPIT_NT_OPT_IN(BM, BN, ST, EPI, CONV, 0);                                                      \
-    hipLaunchKernelGGL((gemm_nt_kernel<T, BM, BN, ST, EPI, CONV>), dim3(unsigned(nb)), dim3(256), shm, s, a, lda, b, \
-                       ldb, c, ldc, M, N, K, ntn, ep, ci, cm, bs, rl, g, bps);                                           \
-    }                                                                                                              \
-  } while (0)
-#define MPIT_NT_LAUNCH2(BM, BN, ST, CONV)                                                         \
-  do {                                                                                              \
-    if (epi == EPI_STATS) MPIT_NT_LAUNCH1(BM, BN, ST, EPI_STATS, CONV);                        \
-    else if (epi == EPI_BNRED) MPIT_NT_LAUNCH1(BM, BN, ST, EPI_BNRED, CONV);                   \
-    else if (epi == EPI_BNRED2 && !CONV) MPIT_NT_LAUNCH1(BM, BN, ST, EPI_BNRED2, false);       \
-    else if (epi == EPI_RELUB && CONV) MPIT_NT_LAUNCH1(BM, BN, ST, EPI_RELUB, true);           \
-    else MPIT_NT_LAUNCH1(BM, BN, ST, EPI_NONE, CONV);                                          \
-  } while (0)
-#define MPIT_NT_LAUNCH(BM, BN, ST)                                                                             \
-  do {                                                                                                         \
-    const int64_t mtn = (M + BM - 1) / BM;                                                                     \
-    const int ntn = N / BN;                                                                                    \
-    const int64_t nb = mtn * ntn;                                                                              \
-    if (nb > INT32_MAX) throw std::invalid_argument("gemm_nt: too many tiles");                               \
-    if (ep.fcoef || ep.scoef) fold_plan(ep, dev, s, mtn, ntn);                                                                 \
-    /* LDS: the k-tile ring, reused by the epilogue's output tile and reduction table */                      \
-    const size_t shm = std::max({size_t(ST) * (size_t(BM) * nt_bkb(BM, BN, fm) +                               \
-                                                (fm == 11 || fm == 13 ? size_t(BN) * 128 : fm == 4 || fm >= 9 ? size_t(BN) * 192 : size_t(BN) * nt_bkb(BM, BN, fm))), \
-                                 size_t(BM) * BN * sizeof(T), size_t(256) * 8 * 3 * sizeof(float)});          \
-    if (geo) MPIT_NT_LAUNCH2(BM, BN, ST, true);                                                           \
-    else MPIT_NT_LAUNCH2(BM, BN, ST, false);                                                              \
-  } while (0)
-  const int tcfg = fm == 4 || fm >= 9 ? 0 : nt_tile_config(M, N, K, geo != nullptr, geo ? geo->C : 0, F32);
-  if constexpr (F32) {
-    // MPIT_F32_TILE=256x64: the fp16x3 GEMMs with N == 64 on 256 x 64 blocks (each wave 64 x 64
-    // instead of 32 x 64: twice the MFMAs per barrier and per A fragment split, 2 blocks/CU)
-    static const bool t256x64 = [] {
-      const char* e = std::getenv("MPIT_F32_TILE");
-      return e && std::string(e) == "256x64";
-    }();
-    if (fm == 11 && N == 64 && t256x64) {  // (FM 13 runs 128-row tiles)
-      MPIT_NT_LAUNCH(256, 64, 2);
-      hip_check(hipGetLastError(), "gemm_nt launch");
-      return;
+  if (ep.fcoef || ep.scoef) fold_plan(ep, dev, s, p.mtn, p.ntn);
+  const ConvGeo g = geo ? *geo : ConvGeo{};
+  // the one launch site of gemm_nt_kernel: the plan's values as template arguments
+  auto launch = [&](auto F32, auto BM, auto BN, auto ST, auto EPI, auto CONV, auto FM) {
+    if constexpr (!nt_built(F32 != 0, BM, BN, ST, EPI, CONV, FM)) {
+      return false;
+    } else {
+      using T = std::conditional_t<F32 != 0, float, uint16_t>;
+      if (p.lds > 65536) {  // once per instantiation (its LDS request is a constant)
+        static const bool opted =
+            (hip_check(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_kernel<T, BM, BN, ST, EPI, (CONV != 0), FM>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, int(p.lds)),
+                       "hipFuncSetAttribute"),
+             true);
+        (void)opted;
+      }
+      hipLaunchKernelGGL((gemm_nt_kernel<T, BM, BN, ST, EPI, (CONV != 0), FM>), dim3(unsigned(p.grid)), dim3(256), p.lds,
+                         s, reinterpret_cast<const T*>(A), lda, reinterpret_cast<const T*>(B), ldb,
+                         reinterpret_cast<T*>(C), ldc, M, N, K, p.ntn, ep, reinterpret_cast<const T*>(cin),
+                         reinterpret_cast<const uint8_t*>(cmask), reinterpret_cast<const float*>(bias), relu ? 1 : 0, g,
+                         bps);
+      return true;
     }
-    if (tcfg == 1) {
-      MPIT_NT_LAUNCH(256, 128, 3);
-      hip_check(hipGetLastError(), "gemm_nt launch");
-      return;
-    }
-  } else {
-    if (tcfg == 2) {
-      MPIT_NT_LAUNCH(256, 256, 2);  // 2 x 64-deep stages = the 128 KB epilogue tile
-      hip_check(hipGetLastError(), "gemm_nt launch");
-      return;
-    }
-    if (tcfg == 1) {
-      MPIT_NT_LAUNCH(256, 128, 3);
-      hip_check(hipGetLastError(), "gemm_nt launch");
-      return;
-    }
-  }
-  // MPIT_F32_BN64=1: fp32 GEMMs on 128x64 tiles (3 blocks per CU instead of 2) — A/B knob
-  static const bool f32_bn64 = [] {
-    const char* e = std::getenv("MPIT_F32_BN64");
-    return e && std::string(e) == "1";
-  }();
-  if (N % 128 == 0 && !(F32 && f32_bn64)) {
-    if (stages == 4) MPIT_NT_LAUNCH(128, 128, 4);
-    else if (stages == 3) MPIT_NT_LAUNCH(128, 128, 3);
-    else MPIT_NT_LAUNCH(128, 128, 2);
-  } else {
-    if (stages == 4) MPIT_NT_LAUNCH(128, 64, 4);
-    else if (stages == 3) MPIT_NT_LAUNCH(128, 64, 3);
-    else MPIT_NT_LAUNCH(128, 64, 2);
-  }
-#undef MPIT_NT_LAUNCH
-#undef MPIT_NT_LAUNCH2
-#undef MPIT_NT_LAUNCH1
-#undef MPIT_NT_OPT_IN
+  };
+  const int key[] = {f32 ? 1 : 0, p.BM, p.BN, p.STAGES, p.EPI, p.CONV, p.FM};
+  if (!dispatch(key, std::tuple_cat(std::tuple<IntList<0, 1>>{}, NtLists{}), launch))
+    throw std::logic_error("gemm_nt: no kernel is built for the planned instantiation");
   hip_check(hipGetLastError(), "gemm_nt launch");
-}
-
-// bps > 0: B is three pre-split bf16 planes (h, m, l) of plane stride bps elements (fp32 only)
-static void launch_nt(int dev, hipStream_t s, int64_t M, int N, int K, uintptr_t A, int64_t lda, uintptr_t B,
-                      int64_t ldb, uintptr_t C, int64_t ldc, uintptr_t cin, uintptr_t cmask, const ConvGeo* geo,
-                      const EpiArgs& ep, int epi, bool f32, uintptr_t bias = 0, bool relu = false, int64_t bps = 0) {
-  if (f32) launch_nt_t<float>(dev, s, M, N, K, A, lda, B, ldb, C, ldc, cin, cmask, geo, ep, epi, bias, relu, bps);
-  else launch_nt_t<uint16_t>(dev, s, M, N, K, A, lda, B, ldb, C, ldc, cin, cmask, geo, ep, epi, bias, relu, bps);
 }
 
 // the reduction epilogue selected by the (stats, BN reduction) operands
@@ -3295,130 +3307,153 @@ void gemm_nt(int dev, hipStream_t s, int64_t M, int N, int K, uintptr_t A, int64
 
 bool gemm_tn_supported(int64_t M, int N, int K) { return M > 0 && N % 64 == 0 && K % 64 == 0 && N > 0 && K > 0; }
 
-// split-K plan: number of splits over M and rows per split, sized so the grid holds
-// about as many blocks as can be resident (bf16 4-stage / fp32 2-stage ring: 64 KiB of
-// LDS per 128x128 tile)
-// MPIT_TN_OCC=1: one gemm_tn block per CU (its LDS request padded to kTnCapShm), so a CU
-// running a backward-weight block of the side stream always has room for one block of the
-// critical path's GEMMs (64 KiB) next to it; the split plan then targets one block per CU.
-constexpr size_t kTnCapShm = 92 * 1024;
-static bool tn_cap1() {
-  static const bool on = [] {
-    const char* e = std::getenv("MPIT_TN_OCC");
-    return e && std::string(e) == "1";
-  }();
-  return on;
-}
+constexpr size_t kTnCapShm = 92 * 1024;  // MPIT_TN_OCC=1: LDS request that leaves one block per CU
 
-static int tn_plan(int dev, int64_t M, int N, int K, int64_t* rows_per_split, int* tbn, int* tbk, int cin = 0) {
-  *tbn = N % 128 == 0 ? 128 : 64;
-  // conv: a column tile never straddles two taps — except the row-tap stem (cin = kStemTap),
-  // whose lanes locate their tap per 16-B chunk: there 128-wide tiles read dY half as often
-  *tbk = (cin && cin != kStemTap ? cin : K) % 128 == 0 ? 128 : 64;
-  const int64_t ntiles = int64_t(N / *tbn) * (K / *tbk);
-  const int per_cu = tn_cap1() ? 1 : 2 * (128 / *tbn) * (128 / *tbk);
-  // MPIT_TN_SPLIT_MUL=k: k times the splits (shorter blocks that free their CU sooner for
-  // the critical path's kernels, at k times the partial-sum traffic) — A/B knob
-  // (MPIT_TN_SPLIT_DIV=k: 1/k of them — longer blocks, less partial-sum traffic)
-  static const int split_mul = [] {
-    const char* e = std::getenv("MPIT_TN_SPLIT_MUL");
-    return e ? std::max(1, std::min(8, std::atoi(e))) : 1;
-  }();
-  static const int split_div = [] {
-    const char* e = std::getenv("MPIT_TN_SPLIT_DIV");
-    return e ? std::max(1, std::min(8, std::atoi(e))) : 1;
-  }();
-  const int64_t target = std::max<int64_t>(1, int64_t(per_cu) * cu_count(dev) * split_mul / split_div);
-  // floor: one more block than there are slots would run as a whole second round
-  int64_t ns = std::max<int64_t>(1, target / ntiles);
-  // keep >= 8 staged steps per block; MPIT_TN_MIN_ROWS=r raises the floor (fewer, longer splits
-  // where M is deep and the output small — less partial-sum traffic; A/B knob)
-  static const int64_t min_rows_env = [] {
-    const char* e = std::getenv("MPIT_TN_MIN_ROWS");
-    return e ? std::max<int64_t>(8 * kRows, std::atoll(e)) : int64_t(8 * kRows);
-  }();
-  const int64_t min_rows = min_rows_env;
-  ns = std::min<int64_t>(ns, std::max<int64_t>(1, M / min_rows));
-  ns = std::min<int64_t>(ns, int64_t(kReduceGroup) * kReduceGroup);  // two reduce levels at most
-  int64_t rps = (M + ns - 1) / ns;
-  rps = (rps + kRows - 1) / kRows * kRows;
-  ns = (M + rps - 1) / rps;
-  *rows_per_split = rps;
-  return int(ns);
-}
+// What a gemm_tn call is ...
+struct TnQuery {
+  bool f32;
+  int64_t M;
+  int N, K;
+  bool conv;
+  int C, pitch;  // ConvGeo fields that matter
+  bool beta0;    // beta == 0
+  bool ws;       // a workspace was given
+  bool amax_y, amax_x;
+  int64_t yps, xps;  // plane strides (fp32 operands given as fp16 planes; 0: not planes)
+  int cus;           // compute units of the device
+};
+// ... and what runs for it: gemm_tn_kernel<T, TBN, TBK, STAGES, CONV, FM, KR> (T 16-bit when
+// f16: bf16 operands, or fp32 ones as fp16 planes) or gemm_tn_f32s_kernel<CONV>
+struct TnPlan {
+  int f16, TBN, TBK, STAGES, CONV, FM, KR;
+  bool f32s;     // gemm_tn_f32s_kernel
+  int splits;    // over M
+  int64_t rps;   // rows per split
+  int ntk, ntiles;
+  int groups;    // first-level reduce groups (0: one level)
+  bool direct;   // one split, beta == 0: the kernel writes `out` itself
+  bool fused;    // the split reduction runs inside the kernel
+  int64_t grid;
+  size_t lds;
+};
 
 static int64_t tn_groups(int ns) { return ns > kReduceGroup ? (ns + kReduceGroup - 1) / kReduceGroup : 0; }
 
-int64_t gemm_tn_ws_floats(int dev, int64_t M, int N, int K) {
-  int64_t rps;
-  int tbn, tbk;
-  const int ns = tn_plan(dev, M, N, K, &rps, &tbn, &tbk);
-  return ns > 1 ? (int64_t(ns) + tn_groups(ns)) * N * K : 0;
+// Pure, as nt_plan. The split-K plan: number of splits over M and rows per split, sized so the
+// grid holds about as many blocks as can be resident (bf16 4-stage / fp32 2-stage ring: 64 KiB
+// of LDS per 128x128 tile).
+static TnPlan tn_plan(const TnQuery& q, const GemmKnobs& kn) {
+  const int N = q.N, K = q.K;
+  const int64_t M = q.M;
+  if (q.f32 && (q.yps > 0 || q.xps > 0)) {  // fp32 operands as fp16 planes: the 16-bit kernel's FM_F16_PLANES
+    if (q.yps <= 0 || q.xps <= 0) throw std::invalid_argument("gemm_tn: both operands must be planes (FM 13)");
+    if (!kn.f32_split) throw std::invalid_argument("gemm_tn: fp16 planes are the fp16x3 path");
+  } else if (!q.f32 && (q.amax_y || q.amax_x || q.yps || q.xps)) {
+    throw std::invalid_argument("gemm_tn: operand bounds are for fp32 (fp16x3) calls");
+  }
+  TnPlan p{};
+  const bool p13 = q.f32 && q.yps > 0;
+  p.f16 = !q.f32 || p13;
+  p.CONV = q.conv ? 1 : 0;
+  p.TBN = N % 128 == 0 ? 128 : 64;
+  // conv: a column tile never straddles two taps — except the row-tap stem (C = kStemTap),
+  // whose lanes locate their tap per 16-B chunk: there 128-wide tiles read dY half as often
+  p.TBK = (q.conv && q.C != kStemTap ? q.C : K) % 128 == 0 ? 128 : 64;
+  p.ntk = K / p.TBK;
+  p.ntiles = (N / p.TBN) * p.ntk;
+  const int per_cu = kn.tn_cap1 ? 1 : 2 * (128 / p.TBN) * (128 / p.TBK);
+  const int64_t target = std::max<int64_t>(1, int64_t(per_cu) * q.cus * kn.split_mul / kn.split_div);
+  // floor: one more block than there are slots would run as a whole second round
+  int64_t ns = std::max<int64_t>(1, target / p.ntiles);
+  ns = std::min<int64_t>(ns, std::max<int64_t>(1, M / kn.min_rows));  // >= 8 staged steps per block
+  ns = std::min<int64_t>(ns, int64_t(kReduceGroup) * kReduceGroup);   // two reduce levels at most
+  int64_t rps = (M + ns - 1) / ns;
+  rps = (rps + kRows - 1) / kRows * kRows;
+  p.rps = rps;
+  p.splits = int((M + rps - 1) / rps);
+  p.groups = int(tn_groups(p.splits));
+  p.grid = int64_t(p.ntiles) * p.splits;
+  p.direct = p.splits == 1 && q.beta0;
+  if (!p.direct && !q.ws) throw std::invalid_argument("gemm_tn: workspace required");
+  if (q.amax_y != q.amax_x) throw std::invalid_argument("gemm_tn: fp16x3 needs both operand bounds");
+  if (p13 && (!q.amax_y || q.xps <= 0 || !kTnBuf || (q.conv && q.pitch)))
+    throw std::invalid_argument("gemm_tn: fp16 planes need both bounds and plane strides");
+  p.fused = !p.direct && kn.tn_fused && int64_t(p.ntiles) * (std::max(p.groups, 1) + 1) <= kTnMaxTickets;
+  // fp32 with both operand bounds: fp16x3, else bf16x6
+  const int tfm = p.f16 || !kn.f32_split ? FM_NATIVE : (q.amax_y ? (kn.f16s ? FM_F16X3_ONCE : FM_F16X3) : FM_X6_K16);
+  const size_t esz = p.f16 ? 2 : 4;
+  if (!p.f16 && tfm == FM_X6_K16 && kn.f32s && !p.fused && p.TBN == 128 && p.TBK == 128 &&
+      (!q.conv || (!q.pitch && q.C % 128 == 0))) {
+    p.f32s = true;
+    p.lds = size_t(2) * 3 * 256 * kTsR * 2;
+  } else if (p13) {  // 32-row steps on a 2-deep ring (FM_F16X3_ONCE's LDS)
+    p.FM = FM_F16_PLANES, p.KR = kRows, p.STAGES = 2;
+    p.lds = size_t(2) * kRows * (p.TBN + p.TBK) * 2 * esz;
+  } else if (p.f16 && kn.kr64_stages && !p.fused) {  // bf16: 64-row steps
+    p.FM = FM_NATIVE, p.KR = 64, p.STAGES = kn.kr64_stages;
+    p.lds = size_t(p.STAGES) * 64 * (p.TBN + p.TBK) * esz;
+  } else {
+    p.FM = tfm, p.KR = kRows, p.STAGES = p.f16 ? kn.tn_stages : 2;
+    p.lds = size_t(p.STAGES) * kRows * (p.TBN + p.TBK) * esz;
+    if (kn.tn_cap1) p.lds = std::max(p.lds, kTnCapShm);
+  }
+  return p;
 }
 
-template <typename T>
-static void launch_tn_t(int dev, hipStream_t s, int64_t M, int N, int K, uintptr_t Y, int64_t ldy, uintptr_t X,
-                        int64_t ldx, uintptr_t out, uintptr_t ws, float beta, const ConvGeo* geo, uintptr_t amax_y,
-                        uintptr_t amax_x, int64_t yps = 0, int64_t xps = 0) {
-  constexpr bool F32 = sizeof(T) == 4;
-  constexpr int EPC = epc<T>();
-  if (!gemm_tn_supported(M, N, K))
-    throw std::invalid_argument("gemm_tn: need N % 64 == 0 and K % 64 == 0");
+// the planner's view of a call for the workspace-size functions (any element type, ws given)
+static TnPlan tn_ws_plan(int dev, int64_t M, int N, int K, int cin) {
+  return tn_plan(TnQuery{false, M, N, K, cin != 0, cin, 0, false, true, false, false, 0, 0, cu_count(dev)}, gemm_knobs());
+}
+static int64_t tn_ws_floats(const TnPlan& p, int N, int K) {
+  return p.splits > 1 ? (int64_t(p.splits) + p.groups) * N * K : 0;
+}
+
+int64_t gemm_tn_ws_floats(int dev, int64_t M, int N, int K) { return tn_ws_floats(tn_ws_plan(dev, M, N, K, 0), N, K); }
+
+// The gemm_tn_kernel instantiations that are built, per element type
+using TnLists = std::tuple<IntList<64, 128>, IntList<64, 128>, IntList<2, 3, 4>, IntList<0, 1>,
+                           IntList<FM_NATIVE, FM_X6_K16, FM_F16X3, FM_F16X3_ONCE, FM_F16_PLANES>, IntList<kRows, 64>>;
+constexpr bool tn_built(bool f32, int TBN, int TBK, int ST, int CONV, int FM, int KR) {
+  if (KR == 64) return !f32 && FM == FM_NATIVE && (ST == 2 || ST == 3);  // 64-row steps: bf16 only
+  if (FM == FM_F16_PLANES) return !f32 && ST == 2;
+  if (ST != 2 && ST != 4) return false;
+  return f32 ? (FM == FM_NATIVE || FM == FM_X6_K16 || FM == FM_F16X3 || FM == FM_F16X3_ONCE) : FM == FM_NATIVE;
+}
+
+static void launch_tn(int dev, hipStream_t s, int64_t M, int N, int K, uintptr_t Y, int64_t ldy, uintptr_t X,
+                      int64_t ldx, uintptr_t out, uintptr_t ws, float beta, const ConvGeo* geo, bool f32,
+                      uintptr_t amax_y = 0, uintptr_t amax_x = 0, int64_t yps = 0, int64_t xps = 0) {
+  const bool f16 = !f32 || yps > 0 || xps > 0;  // the kernel's element type (fp32 planes: 16-bit)
+  const int EPC = f16 ? epc<uint16_t>() : epc<float>();
+  if (!gemm_tn_supported(M, N, K)) throw std::invalid_argument("gemm_tn: need N % 64 == 0 and K % 64 == 0");
   check_ptr(Y, "Y");
   check_ptr(X, "X");
   check_ptr(out, "out");
-  if (ldy % EPC || ldx % EPC || ldy < N || (!geo && ldx < K))
-    throw std::invalid_argument("gemm_tn: bad leading dimensions");
+  if (ldy % EPC || ldx % EPC || ldy < N || (!geo && ldx < K)) throw std::invalid_argument("gemm_tn: bad leading dimensions");
   hip_check(hipSetDevice(dev), "hipSetDevice");
-  int64_t rps;
-  int tbn, tbk;
-  const int ns = tn_plan(dev, M, N, K, &rps, &tbn, &tbk, geo ? geo->C : 0);
-  if (gemm_log())
+  const TnPlan p = tn_plan(TnQuery{f32, M, N, K, geo != nullptr, geo ? geo->C : 0, geo ? geo->pitch : 0, beta == 0.f,
+                                   ws != 0, amax_y != 0, amax_x != 0, yps, xps, cu_count(dev)},
+                           gemm_knobs());
+  const int ns = p.splits;
+  if (gemm_knobs().log)
     std::fprintf(stderr, "MPIT_GEMM tn %lld %d %d conv=%d splits=%d f32=%d\n", (long long)M, N, K, geo ? 1 : 0, ns,
-                 F32 ? 1 : 0);
+                 p.f16 ? 0 : 1);
   if (geo && kTnBuf) {  // buffer-descriptor staging: a split's images span < 2^31 bytes
     const int64_t hw = int64_t(geo->Ho) * geo->Wo;
-    const int64_t imgs = std::min<int64_t>((M + hw - 1) / hw, (rps + hw - 1) / hw + 1);
-    if (imgs * geo->H * geo->W * int64_t(geo->pitch ? geo->pitch : geo->C) * int64_t(sizeof(T)) >= (int64_t(1) << 31))
+    const int64_t imgs = std::min<int64_t>((M + hw - 1) / hw, (p.rps + hw - 1) / hw + 1);
+    if (imgs * geo->H * geo->W * int64_t(geo->pitch ? geo->pitch : geo->C) * (p.f16 ? 2 : 4) >= (int64_t(1) << 31))
       throw std::invalid_argument("gemm_tn: the images of one split span >= 2 GiB");
   }
-  const int ntk = K / tbk;
-  const int ntiles = (N / tbn) * ntk;
-  const bool direct = ns == 1 && beta == 0.f;
-  if (!direct && ws == 0) throw std::invalid_argument("gemm_tn: workspace required");
-  if (!direct) check_ptr(ws, "ws");
-  float* part = reinterpret_cast<float*>(direct ? out : ws);
-  const auto* y = reinterpret_cast<const T*>(Y);
-  const auto* x = reinterpret_cast<const T*>(X);
+  if (!p.direct) check_ptr(ws, "ws");
+  float* part = reinterpret_cast<float*>(p.direct ? out : ws);
   const ConvGeo g = geo ? *geo : ConvGeo{};
-  const dim3 grid(unsigned(int64_t(ntiles) * ns));
-  // MPIT_TN_FUSED=1: the split reduction runs inside the GEMM (last block per tile / group).
-  // Bitwise equal to the split_reduce launches but slower on ResNet-50's wgrads (the tail sum
-  // of a tile is left to one block: profiles/tn_fused_reduction_ab_r02.md), so opt-in.
-  static const bool fused_env = [] {
-    const char* e = std::getenv("MPIT_TN_FUSED");
-    return e && std::string(e) == "1";
-  }();
+  const dim3 grid{unsigned(p.grid)};
   TnRed red{};
-  // fp32 with both operand bounds: fp16x3 (FM 11), else bf16x6 (FM 1)
-  if ((amax_y != 0) != (amax_x != 0)) throw std::invalid_argument("gemm_tn: fp16x3 needs both operand bounds");
-  // fp16x3 wgrad: FM 12 (split once per element into fp16 planes in LDS, transposed fragment
-  // reads) unless MPIT_TN_F16S=0 (FM 11: split per use after column reads)
-  static const bool f16s = [] {
-    const char* e = std::getenv("MPIT_TN_F16S");
-    return !(e && std::string(e) == "0");
-  }();
-  const int tfm = !F32 || f32_mode() != 1 ? 0 : (amax_y ? (f16s ? 12 : 11) : 1);
   red.amax_y = reinterpret_cast<const float*>(amax_y);
   red.amax_x = reinterpret_cast<const float*>(amax_x);
-  red.yps = yps;
-  red.xps = xps;
-  const bool p13 = !F32 && yps > 0;  // fp32 operands as fp16 planes (launch_tn)
-  if (p13 && (!amax_y || !amax_x || xps <= 0 || !kTnBuf || (geo && geo->pitch)))
-    throw std::invalid_argument("gemm_tn: fp16 planes need both bounds and plane strides");
-  const int ngr = ns > kReduceGroup ? int(tn_groups(ns)) : 1;
-  const bool fused = !direct && fused_env && int64_t(ntiles) * (ngr + 1) <= kTnMaxTickets;
-  if (fused) {
+  red.yps = p.f16 && f32 ? yps : 0;
+  red.xps = p.f16 && f32 ? xps : 0;
+  if (p.fused) {
     static std::atomic<uint32_t> launches{0};
     uint32_t* base = nullptr;
     hip_check(hipGetSymbolAddress(reinterpret_cast<void**>(&base), HIP_SYMBOL(g_tn_tickets)), "tn ticket symbol");
@@ -3427,208 +3462,58 @@ static void launch_tn_t(int dev, hipStream_t s, int64_t M, int N, int K, uintptr
     red.mid = part + int64_t(ns) * N * K;
     red.beta = beta;
     red.ns = ns;
-    red.groups = ngr;
+    red.groups = std::max(p.groups, 1);
   }
-  // MPIT_GEMM_TN_STAGES: ring depth (A/B measurements; bf16 4 by default). fp32 stages
-  // twice the bytes per row and computes 16x longer per staged step: 2 stages.
-  static const int tn_stages = [] {
-    const char* e = std::getenv("MPIT_GEMM_TN_STAGES");
-    return e && std::atoi(e) <= 2 ? 2 : 4;
-  }();
-  const int stages = F32 || p13 ? 2 : tn_stages;
-  // fp32 128 x 128 tiles, MPIT_TN_F32S=1: the split-once kernel (experiment; bitwise equal,
-  // slower so far: profiles/wgrad_split_once_r03.md)
-  static const bool f32s = [] {
-    const char* e = std::getenv("MPIT_TN_F32S");
-    return e && std::string(e) == "1";
-  }();
-  if (F32 && tfm == 1 && f32s && !fused && tbn == 128 && tbk == 128 && (!geo || (!geo->pitch && geo->C % 128 == 0))) {
-    const size_t shm = size_t(2) * 3 * 256 * kTsR * 2;
-    const auto* yf = reinterpret_cast<const float*>(Y);
-    const auto* xf = reinterpret_cast<const float*>(X);
-    if (geo)
-      hipLaunchKernelGGL(gemm_tn_f32s_kernel<true>, grid, dim3(256), shm, s, yf, ldy, xf, ldx, part, M, N, K, rps, ntk,
-                         ntiles, g);
-    else
-      hipLaunchKernelGGL(gemm_tn_f32s_kernel<false>, grid, dim3(256), shm, s, yf, ldy, xf, ldx, part, M, N, K, rps,
-                         ntk, ntiles, g);
+  if (p.f32s) {
+    // the one launch site of gemm_tn_f32s_kernel
+    auto launch = [&](auto CONV) {
+      hipLaunchKernelGGL(gemm_tn_f32s_kernel<(CONV != 0)>, grid, dim3(256), p.lds, s, reinterpret_cast<const float*>(Y),
+                         ldy, reinterpret_cast<const float*>(X), ldx, part, M, N, K, p.rps, p.ntk, p.ntiles, g);
+      return true;
+    };
+    dispatch(&p.CONV, std::tuple<IntList<0, 1>>{}, launch);
   } else {
-#define MPIT_TN_OPT_IN(A, B, ST, CV, FMV)                                                                          \
-  do {                                                                                                             \
-    static const bool opted = (hip_check(hipFuncSetAttribute(reinterpret_cast<const void*>(                       \
-                                                             &gemm_tn_kernel<T, A, B, ST, CV, FMV>),              \
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, int(shm)),    \
-                                     "hipFuncSetAttribute"),                                                       \
-                               true);                                                                              \
-    (void)opted;                                                                                                   \
-  } while (0)
-#define MPIT_TN_LAUNCH1(A, B, ST)                                                                                  \
-  do {                                                                                                             \
-    size_t shm = size_t(ST) * kRows * (tbn + tbk) * sizeof(T);                                                   \
-    if (tn_cap1()) {                                                                                               \
-      shm = std::max(shm, kTnCapShm);                                                                              \
-      if (geo && F32 && tfm == 12) MPIT_TN_OPT_IN(A, B, ST, true, F32 ? 12 : 0);                                   \
-      else if (F32 && tfm == 12) MPIT_TN_OPT_IN(A, B, ST, false, F32 ? 12 : 0);                                    \
-      else if (geo && F32 && tfm == 11) MPIT_TN_OPT_IN(A, B, ST, true, F32 ? 11 : 0);                              \
-      else if (F32 && tfm == 11) MPIT_TN_OPT_IN(A, B, ST, false, F32 ? 11 : 0);                                    \
-      else if (geo && F32 && f32_mode() == 1) MPIT_TN_OPT_IN(A, B, ST, true, F32 ? 1 : 0);                         \
-      else if (F32 && f32_mode() == 1) MPIT_TN_OPT_IN(A, B, ST, false, F32 ? 1 : 0);                               \
-      else if (geo) MPIT_TN_OPT_IN(A, B, ST, true, 0);                                                             \
-      else MPIT_TN_OPT_IN(A, B, ST, false, 0);                                                                     \
-    }                                                                                                              \
-    if (geo && F32 && tfm == 12)                                                                                   \
-      hipLaunchKernelGGL((gemm_tn_kernel<T, A, B, ST, true, F32 ? 12 : 0>), grid, dim3(256), shm, s, y, ldy, x,    \
-                         ldx, part, M, N, K, rps, ntk, ntiles, g, red);                                            \
-    else if (F32 && tfm == 12)                                                                                     \
-      hipLaunchKernelGGL((gemm_tn_kernel<T, A, B, ST, false, F32 ? 12 : 0>), grid, dim3(256), shm, s, y, ldy, x,   \
-                         ldx, part, M, N, K, rps, ntk, ntiles, g, red);                                            \
-    else if (geo && F32 && tfm == 11)                                                                              \
-      hipLaunchKernelGGL((gemm_tn_kernel<T, A, B, ST, true, F32 ? 11 : 0>), grid, dim3(256), shm, s, y, ldy, x,    \
-                         ldx, part, M, N, K, rps, ntk, ntiles, g, red);                                            \
-    else if (F32 && tfm == 11)                                                                                     \
-      hipLaunchKernelGGL((gemm_tn_kernel<T, A, B, ST, false, F32 ? 11 : 0>), grid, dim3(256), shm, s, y, ldy, x,   \
-                         ldx, part, M, N, K, rps, ntk, ntiles, g, red);                                            \
-    else if (geo && F32 && f32_mode() == 1)                                                                        \
-      hipLaunchKernelGGL((gemm_tn_kernel<T, A, B, ST, true, F32 ? 1 : 0>), grid, dim3(256), shm, s, y, ldy, x,     \
-                         ldx, part, M, N, K, rps, ntk, ntiles, g, red);                                            \
-    else if (F32 && f32_mode() == 1)                                                                               \
-      hipLaunchKernelGGL((gemm_tn_kernel<T, A, B, ST, false, F32 ? 1 : 0>), grid, dim3(256), shm, s, y, ldy, x,    \
-                         ldx, part, M, N, K, rps, ntk, ntiles, g, red);                                            \
-    else if (geo)                                                                                                  \
-      hipLaunchKernelGGL((gemm_tn_kernel<T, A, B, ST, true>), grid, dim3(256), shm, s, y, ldy, x, ldx, part, M, N, \
-                         K, rps, ntk, ntiles, g, red);                                                             \
-    else                                                                                                           \
-      hipLaunchKernelGGL((gemm_tn_kernel<T, A, B, ST, false>), grid, dim3(256), shm, s, y, ldy, x, ldx, part, M,   \
-                         N, K, rps, ntk, ntiles, g, red);                                                          \
-  } while (0)
-#define MPIT_TN_LAUNCH(A, B)               \
-  do {                                     \
-    if (stages == 2) MPIT_TN_LAUNCH1(A, B, 2); \
-    else MPIT_TN_LAUNCH1(A, B, 4);         \
-  } while (0)
-  // bf16: 64-row staged steps on a 2-deep ring (MPIT_TN_KR_STAGES=3: 3-deep) — the LDS of a
-  // 4 x 32-row ring, half its barriers per row. Default since r05o: VGG-16 bf16 5,557 vs 5,480
-  // img/s, ResNet-50 bf16 11,674 vs 11,596 (r05d). MPIT_TN_KROWS=32: the 4 x 32-row ring
-  static const int kr64_stages = [] {
-    const char* e = std::getenv("MPIT_TN_KROWS");
-    if (e && std::atoi(e) == 32) return 0;
-    const char* st = std::getenv("MPIT_TN_KR_STAGES");
-    return st && std::atoi(st) == 3 ? 3 : 2;
-  }();
-  bool done64 = false;
-  if constexpr (!F32) {
-    if (p13) {  // fp16x3 planes: 32-row steps on a 2-deep ring (FM 12's LDS)
-#define MPIT_TN_P13(A, B)                                                                                          \
-  do {                                                                                                             \
-    const size_t shm = size_t(2) * kRows * (tbn + tbk) * 2 * sizeof(T);                                             \
-    if (geo) {                                                                                                     \
-      if (shm > 65536) MPIT_TN_OPT_IN13(A, B, true);                                                               \
-      hipLaunchKernelGGL((gemm_tn_kernel<T, A, B, 2, true, 13, kRows>), grid, dim3(256), shm, s, y, ldy, x, ldx,   \
-                         part, M, N, K, rps, ntk, ntiles, g, red);                                                 \
-    } else {                                                                                                       \
-      if (shm > 65536) MPIT_TN_OPT_IN13(A, B, false);                                                              \
-      hipLaunchKernelGGL((gemm_tn_kernel<T, A, B, 2, false, 13, kRows>), grid, dim3(256), shm, s, y, ldy, x, ldx,  \
-                         part, M, N, K, rps, ntk, ntiles, g, red);                                                 \
-    }                                                                                                              \
-  } while (0)
-#define MPIT_TN_OPT_IN13(A, B, CV)                                                                                 \
-  do {                                                                                                             \
-    static const bool opted = (hip_check(hipFuncSetAttribute(reinterpret_cast<const void*>(                       \
-                                                             &gemm_tn_kernel<T, A, B, 2, CV, 13, kRows>),         \
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, int(shm)),    \
-                                     "hipFuncSetAttribute"),                                                       \
-                               true);                                                                              \
-    (void)opted;                                                                                                   \
-  } while (0)
-      if (tbn == 128 && tbk == 128) MPIT_TN_P13(128, 128);
-      else if (tbn == 128) MPIT_TN_P13(128, 64);
-      else if (tbk == 128) MPIT_TN_P13(64, 128);
-      else MPIT_TN_P13(64, 64);
-#undef MPIT_TN_P13
-#undef MPIT_TN_OPT_IN13
-      done64 = true;
-    }
-    if (!done64 && kr64_stages && !fused) {
-#define MPIT_TN_K64(A, B, ST)                                                                                      \
-  do {                                                                                                             \
-    const size_t shm = size_t(ST) * 64 * (tbn + tbk) * sizeof(T);                                                  \
-    if (geo) {                                                                                                     \
-      if (shm > 65536) MPIT_TN_OPT_IN64(A, B, ST, true);                                                           \
-      hipLaunchKernelGGL((gemm_tn_kernel<T, A, B, ST, true, 0, 64>), grid, dim3(256), shm, s, y, ldy, x, ldx, part, \
-                         M, N, K, rps, ntk, ntiles, g, red);                                                       \
-    } else {                                                                                                       \
-      if (shm > 65536) MPIT_TN_OPT_IN64(A, B, ST, false);                                                          \
-      hipLaunchKernelGGL((gemm_tn_kernel<T, A, B, ST, false, 0, 64>), grid, dim3(256), shm, s, y, ldy, x, ldx,    \
-                         part, M, N, K, rps, ntk, ntiles, g, red);                                                 \
-    }                                                                                                              \
-  } while (0)
-#define MPIT_TN_OPT_IN64(A, B, ST, CV)                                                                             \
-  do {                                                                                                             \
-    static const bool opted = (hip_check(hipFuncSetAttribute(reinterpret_cast<const void*>(                       \
-                                                             &gemm_tn_kernel<T, A, B, ST, CV, 0, 64>),            \
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, int(shm)),    \
-                                     "hipFuncSetAttribute"),                                                       \
-                               true);                                                                              \
-    (void)opted;                                                                                                   \
-  } while (0)
-#define MPIT_TN_K64S(A, B)                  \
-  do {                                      \
-    if (kr64_stages == 3) MPIT_TN_K64(A, B, 3); \
-    else MPIT_TN_K64(A, B, 2);              \
-  } while (0)
-      if (tbn == 128 && tbk == 128) MPIT_TN_K64S(128, 128);
-      else if (tbn == 128) MPIT_TN_K64S(128, 64);
-      else if (tbk == 128) MPIT_TN_K64S(64, 128);
-      else MPIT_TN_K64S(64, 64);
-#undef MPIT_TN_K64S
-#undef MPIT_TN_K64
-#undef MPIT_TN_OPT_IN64
-      done64 = true;
-    }
+    // the one launch site of gemm_tn_kernel: the plan's values as template arguments
+    auto launch = [&](auto F32, auto TBN, auto TBK, auto ST, auto CONV, auto FM, auto KR) {
+      if constexpr (!tn_built(F32 != 0, TBN, TBK, ST, CONV, FM, KR)) {
+        return false;
+      } else {
+        using T = std::conditional_t<F32 != 0, float, uint16_t>;
+        if (p.lds > 65536) {  // once per instantiation (its LDS request is a constant)
+          static const bool opted =
+              (hip_check(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_kernel<T, TBN, TBK, ST, (CONV != 0), FM, KR>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, int(p.lds)),
+                         "hipFuncSetAttribute"),
+               true);
+          (void)opted;
+        }
+        hipLaunchKernelGGL((gemm_tn_kernel<T, TBN, TBK, ST, (CONV != 0), FM, KR>), grid, dim3(256), p.lds, s,
+                           reinterpret_cast<const T*>(Y), ldy, reinterpret_cast<const T*>(X), ldx, part, M, N, K, p.rps,
+                           p.ntk, p.ntiles, g, red);
+        return true;
+      }
+    };
+    const int key[] = {p.f16 ? 0 : 1, p.TBN, p.TBK, p.STAGES, p.CONV, p.FM, p.KR};
+    if (!dispatch(key, std::tuple_cat(std::tuple<IntList<0, 1>>{}, TnLists{}), launch))
+      throw std::logic_error("gemm_tn: no kernel is built for the planned instantiation");
   }
-  if (!done64) {
-  if (tbn == 128 && tbk == 128) MPIT_TN_LAUNCH(128, 128);
-  else if (tbn == 128) MPIT_TN_LAUNCH(128, 64);
-  else if (tbk == 128) MPIT_TN_LAUNCH(64, 128);
-  else MPIT_TN_LAUNCH(64, 64);
-  }
-  }
-#undef MPIT_TN_LAUNCH
-#undef MPIT_TN_LAUNCH1
-#undef MPIT_TN_OPT_IN
   hip_check(hipGetLastError(), "gemm_tn launch");
-  if (!direct && !fused) {
+  if (!p.direct && !p.fused) {
     const int64_t n4 = int64_t(N) * K / 4;
     const unsigned gx = unsigned((n4 + 255) / 256);
-    const int64_t groups = tn_groups(ns);
     const float4* src = reinterpret_cast<const float4*>(part);
     int nsrc = ns;
-    if (groups) {  // level 1: groups of kReduceGroup splits -> ws tail
+    if (p.groups) {  // level 1: groups of kReduceGroup splits -> ws tail
       float4* mid = reinterpret_cast<float4*>(part + int64_t(ns) * N * K);
-      hipLaunchKernelGGL(split_reduce_kernel, dim3(gx, unsigned(groups)), dim3(256), 0, s, src, ns, n4, mid, beta);
+      hipLaunchKernelGGL(split_reduce_kernel, dim3(gx, unsigned(p.groups)), dim3(256), 0, s, src, ns, n4, mid, beta);
       hip_check(hipGetLastError(), "gemm_tn reduce launch");
       src = mid;
-      nsrc = int(groups);
+      nsrc = p.groups;
     }
     hipLaunchKernelGGL(split_reduce_kernel, dim3(gx, 1), dim3(256), 0, s, src, nsrc, n4,
                        reinterpret_cast<float4*>(out), beta);
     hip_check(hipGetLastError(), "gemm_tn reduce launch");
   }
-}
-
-static void launch_tn(int dev, hipStream_t s, int64_t M, int N, int K, uintptr_t Y, int64_t ldy, uintptr_t X,
-                      int64_t ldx, uintptr_t out, uintptr_t ws, float beta, const ConvGeo* geo, bool f32,
-                      uintptr_t amax_y = 0, uintptr_t amax_x = 0, int64_t yps = 0, int64_t xps = 0) {
-  // fp32 operands given as fp16 planes (yps / xps > 0): the 16-bit kernel's FM 13
-  if (f32 && (yps > 0 || xps > 0)) {
-    if (yps <= 0 || xps <= 0) throw std::invalid_argument("gemm_tn: both operands must be planes (FM 13)");
-    if (f32_mode() != 1) throw std::invalid_argument("gemm_tn: fp16 planes are the fp16x3 path");
-    launch_tn_t<uint16_t>(dev, s, M, N, K, Y, ldy, X, ldx, out, ws, beta, geo, amax_y, amax_x, yps, xps);
-    return;
-  }
-  if (f32) launch_tn_t<float>(dev, s, M, N, K, Y, ldy, X, ldx, out, ws, beta, geo, amax_y, amax_x);
-  else if (amax_y || amax_x || yps || xps) throw std::invalid_argument("gemm_tn: operand bounds are for fp32 (fp16x3) calls");
-  else launch_tn_t<uint16_t>(dev, s, M, N, K, Y, ldy, X, ldx, out, ws, beta, geo, 0, 0);
 }
 
 void gemm_tn(int dev, hipStream_t s, int64_t M, int N, int K, uintptr_t Y, int64_t ldy, uintptr_t X, int64_t ldx,
@@ -3667,10 +3552,7 @@ int64_t conv_wgrad_ws_floats(int dev, int Nb, int H, int W, int C, int Co, int R
   conv_geo(H, W, C, R, S, stride, pad, &Ho, &Wo);
   const int64_t M = int64_t(Nb) * Ho * Wo;
   const int K = R * S * C;
-  int64_t rps;
-  int tbn, tbk;
-  const int ns = tn_plan(dev, M, Co, K, &rps, &tbn, &tbk, C);
-  return ns > 1 ? (int64_t(ns) + tn_groups(ns)) * Co * K : 0;
+  return tn_ws_floats(tn_ws_plan(dev, M, Co, K, C), Co, K);
 }
 
 void conv_wgrad(int dev, hipStream_t s, int Nb, int H, int W, int C, int Co, int R, int S, int stride, int pad,
@@ -3715,10 +3597,7 @@ void conv_stem_fwd(int dev, hipStream_t s, int Nb, int Hp, int Wp, int Co, int H
 
 int64_t conv_stem_wgrad_ws_floats(int dev, int Nb, int Ho, int Wo, int Co, int rows) {
   const int K = stem_wgrad_rows(rows) * kStemTap;
-  int64_t rps;
-  int tbn, tbk;
-  const int ns = tn_plan(dev, int64_t(Nb) * Ho * Wo, Co, K, &rps, &tbn, &tbk, kStemTap);
-  return ns > 1 ? (int64_t(ns) + tn_groups(ns)) * Co * K : 0;
+  return tn_ws_floats(tn_ws_plan(dev, int64_t(Nb) * Ho * Wo, Co, K, kStemTap), Co, K);
 }
 
 void conv_stem_wgrad(int dev, hipStream_t s, int Nb, int Hp, int Wp, int Co, int Ho, int Wo, int stride, uintptr_t dy,
@@ -3921,6 +3800,41 @@ void conv_dgrad_strided(int dev, hipStream_t s, int Nb, int H, int W, int C, int
     launch_nt(dev, s, M, C, K, dy, Co, wcls + uintptr_t(c.base) * (f32 && !bps ? 4 : 2), K, dx, C, 0, 0, &g, ep, mode,
               f32, 0, false, bps);
   }
+}
+
+// ---- read-only queries of the planners the launchers call (tests/test_gemm_plan.py) ------
+std::map<std::string, int64_t> gemm_nt_plan(bool f32, int64_t M, int N, int K, int C, int pitch, int ostr, int epi,
+                                            int64_t lda, int64_t ldb, int64_t bps, bool amax_a, bool amax_b,
+                                            int64_t aps) {
+  nt_check_shape(M, N, K, f32);
+  const NtPlan p =
+      nt_plan(NtQuery{f32, M, N, K, C != 0, C, pitch, ostr, epi, lda, ldb, bps, aps, amax_a, amax_b}, gemm_knobs());
+  return {{"f32", f32},   {"BM", p.BM}, {"BN", p.BN},   {"STAGES", p.STAGES}, {"EPI", p.EPI},   {"CONV", p.CONV},
+          {"FM", p.FM},   {"bk", p.bk}, {"mtn", p.mtn}, {"ntn", p.ntn},       {"grid", p.grid}, {"lds", int64_t(p.lds)}};
+}
+
+std::map<std::string, int64_t> gemm_tn_plan(int dev, bool f32, int64_t M, int N, int K, int C, int pitch, float beta,
+                                            bool ws, bool amax_y, bool amax_x, int64_t yps, int64_t xps) {
+  if (!gemm_tn_supported(M, N, K)) throw std::invalid_argument("gemm_tn: need N % 64 == 0 and K % 64 == 0");
+  const TnPlan p = tn_plan(
+      TnQuery{f32, M, N, K, C != 0, C, pitch, beta == 0.f, ws, amax_y, amax_x, yps, xps, cu_count(dev)}, gemm_knobs());
+  return {{"f32", !p.f16},       {"f32s", p.f32s},     {"TBN", p.TBN},       {"TBK", p.TBK},
+          {"STAGES", p.STAGES},  {"CONV", p.CONV},     {"FM", p.FM},         {"KR", p.KR},
+          {"splits", p.splits},  {"rps", p.rps},       {"groups", p.groups}, {"direct", p.direct},
+          {"fused", p.fused},    {"grid", p.grid},     {"lds", int64_t(p.lds)}};
+}
+
+// every built instantiation as (f32, template arguments...)
+std::vector<std::vector<int>> gemm_nt_built() {
+  std::vector<std::vector<int>> out;
+  enumerate(out, nt_built, std::tuple_cat(std::tuple<IntList<0, 1>>{}, NtLists{}));
+  return out;
+}
+
+std::vector<std::vector<int>> gemm_tn_built() {
+  std::vector<std::vector<int>> out;
+  enumerate(out, tn_built, std::tuple_cat(std::tuple<IntList<0, 1>>{}, TnLists{}));
+  return out;
 }
 
 }  // namespace mpit

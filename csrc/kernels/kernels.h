@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <array>
+#include <map>
+#include <string>
 #include <vector>
 
 namespace mpit {
@@ -204,6 +206,19 @@ void gemm_nt(int dev, hipStream_t s, int64_t M, int N, int K, uintptr_t A, int64
 // out[N,K] (fp32) = beta*out + Y[M,N]^T . X[M,K]  (split over M; ws: gemm_tn_ws_floats)
 bool gemm_tn_supported(int64_t M, int N, int K);
 int64_t gemm_tn_ws_floats(int dev, int64_t M, int N, int K);
+// Read-only queries of the planners the launchers themselves call (gemm.hip nt_plan / tn_plan):
+// the kernel instantiation, grid and dynamic LDS a call with these operands would run, as named
+// fields; C / pitch / ostr are the ConvGeo's (C == 0: a plain GEMM), the strides and flags say
+// which optional operands are present. Throws what the launch would throw for the combination.
+// dev < 0: no GPU is touched (256 CUs). gemm_*_built: every instantiation that is compiled, as
+// (f32, template arguments...).
+std::map<std::string, int64_t> gemm_nt_plan(bool f32, int64_t M, int N, int K, int C, int pitch, int ostr, int epi,
+                                            int64_t lda, int64_t ldb, int64_t bps, bool amax_a, bool amax_b,
+                                            int64_t aps);
+std::map<std::string, int64_t> gemm_tn_plan(int dev, bool f32, int64_t M, int N, int K, int C, int pitch, float beta,
+                                            bool ws, bool amax_y, bool amax_x, int64_t yps, int64_t xps);
+std::vector<std::vector<int>> gemm_nt_built();
+std::vector<std::vector<int>> gemm_tn_built();
 // compute units of device `dev`; a stream restricted to the CUs of `mask` (gemm.hip)
 int device_cu_count(int dev);
 uintptr_t stream_create_cu_masked(int dev, const std::vector<uint32_t>& mask);

@@ -331,7 +331,7 @@ void maxpool_bwd_t(int dev, hipStream_t s, int N, int H, int W, int C, int K, in
   const auto* y = reinterpret_cast<const T*>(ypool);
   float* part = reinterpret_cast<float*>(ws);
   // windows that partition the input (K == stride, no padding): one thread per window
-  const bool part_win = K == stride && pad == 0 && std::getenv("MPIT_POOL_GATHER") == nullptr;
+  const bool part_win = K == stride && pad == 0 && !env_set("MPIT_POOL_GATHER");
   const int64_t work = part_win ? int64_t(N) * g.Ho * g.Wo * (C / 8) : int64_t(N) * H * W * (C / 8);
   const unsigned grid = ypool ? unsigned(std::min<int64_t>((work + 255) / 256, kPoolRbBlocks)) : grid_for(work);
   const bool narrow = int64_t(N) * H * W * (C / 8) + int64_t(grid) * 256 < (int64_t(1) << 32);

@@ -637,7 +637,7 @@ def worker_cases(env):
     """The reduced list the variant worker runs under the knobs `env` sets."""
     ms = (1, 129, 257)
     paths = NT_PATHS
-    # launch_nt_t: "pre-split B planes need the fp32 bf16x6 path with K % 32 == 0" — the native
+    # nt_plan: "pre-split B planes need the fp32 bf16x6 path with K % 32 == 0" — the native
     # fp32 MFMA and the 16-deep k-tile builds have no planes kernels
     if env.get("MPIT_F32_MFMA") == "native" or env.get("MPIT_F32_BK") == "16":
         paths = ("bf16", "f32")

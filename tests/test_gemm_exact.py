@@ -200,7 +200,11 @@ def test_conv_exact(path):
 
 # ------------------------------------------------------------------ 5. build variants
 VARIANTS = ({"MPIT_GEMM_TILE": "256"}, {"MPIT_GEMM_TILE": "256x128"}, {"MPIT_GEMM_STAGES": "4"},
-            {"MPIT_F32_MFMA": "native"}, {"MPIT_F32_BK": "16"}, {"MPIT_TN_FUSED": "1"}, {"MPIT_TN_KROWS": "64"})
+            {"MPIT_F32_MFMA": "native"}, {"MPIT_F32_BK": "16"}, {"MPIT_TN_FUSED": "1"}, {"MPIT_TN_KROWS": "64"},
+            # the bf16 4 x 32-row ring (KROWS=64 is the default's 64-row steps), 4 and 2 deep
+            {"MPIT_TN_KROWS": "32"}, {"MPIT_TN_KROWS": "32", "MPIT_GEMM_TN_STAGES": "2"},
+            {"MPIT_TN_KR_STAGES": "3"}, {"MPIT_TN_F16S": "0"}, {"MPIT_TN_OCC": "1"},
+            {"MPIT_F32_BN64": "1"}, {"MPIT_F32_TILE": "256x64"})
 # a child takes 3.1 - 3.6 s on an MI355X machine (import, 520 - 700 launches, save; measured per
 # setting); the limit leaves room for a cold file cache
 CHILD_TIMEOUT = 60
