@@ -607,6 +607,16 @@ PYBIND11_MODULE(_mpit, m) {
            py::arg("member"), py::arg("off"), py::arg("loops"), py::arg("table"), py::arg("R"), py::arg("L"),
            py::arg("per"), py::arg("unit"), py::arg("lo"), py::arg("hi"), py::arg("packed"), py::arg("stream"),
            py::call_guard<py::gil_scoped_release>())
+      .def("accumulate_plan",
+           [](Window& w, int m, int64_t off, std::vector<std::array<int64_t, 2>> loops, uintptr_t table, int64_t R,
+              int64_t L, int64_t per, int unit, int64_t lo, int64_t hi, int op, int dtype, uintptr_t packed,
+              uintptr_t fetch, uintptr_t s) {
+             w.accumulate_plan(m, off, CopyPlan{std::move(loops), table, R, L, per, unit, lo, hi}, op, dtype, packed,
+                               fetch, S(s));
+           },
+           py::arg("member"), py::arg("off"), py::arg("loops"), py::arg("table"), py::arg("R"), py::arg("L"),
+           py::arg("per"), py::arg("unit"), py::arg("lo"), py::arg("hi"), py::arg("op"), py::arg("dtype"),
+           py::arg("packed"), py::arg("fetch"), py::arg("stream"), py::call_guard<py::gil_scoped_release>())
       .def("lock", &Window::lock, py::call_guard<py::gil_scoped_release>())
       .def("try_lock", &Window::try_lock)
       .def("unlock", &Window::unlock)
@@ -637,6 +647,17 @@ PYBIND11_MODULE(_mpit, m) {
       py::arg("dev"), py::arg("stream"), py::arg("dir"), py::arg("strided"), py::arg("packed"), py::arg("loops"),
       py::arg("table"), py::arg("R"), py::arg("L"), py::arg("per"), py::arg("unit"), py::arg("max_blocks") = 0,
       py::arg("wide") = false, py::call_guard<py::gil_scoped_release>());
+  m.def("type_accumulate_supported", &type_accumulate_supported, py::arg("op"), py::arg("dtype"));
+  m.def(
+      "type_accumulate",
+      [](int dev, uintptr_t s, int op, int dtype, uintptr_t strided, uintptr_t packed, uintptr_t fetch,
+         std::vector<std::array<int64_t, 2>> loops, uintptr_t table, int64_t R, int64_t L, int64_t per, int unit,
+         int max_blocks, bool wide) {
+        type_accumulate(dev, S(s), op, dtype, strided, packed, fetch, loops, table, R, L, per, unit, max_blocks, wide);
+      },
+      py::arg("dev"), py::arg("stream"), py::arg("op"), py::arg("dtype"), py::arg("strided"), py::arg("packed"),
+      py::arg("fetch"), py::arg("loops"), py::arg("table"), py::arg("R"), py::arg("L"), py::arg("per"),
+      py::arg("unit"), py::arg("max_blocks") = 0, py::arg("wide") = false, py::call_guard<py::gil_scoped_release>());
 
   py::class_<ServerRule>(m, "ServerRule")
       .def(py::init<>())

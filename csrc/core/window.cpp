@@ -195,14 +195,20 @@ void Window::get(uintptr_t dst, int m, int64_t off, int64_t n, hipStream_t s) {
   }
 }
 
+uintptr_t Window::plan_base(int m, int64_t off, const CopyPlan& p, const char* outside) const {
+  const Remote& r = remote_.at(size_t(m));
+  if (p.lo > p.hi) throw std::invalid_argument("mpit: one-sided plan with lo > hi");
+  if (p.hi == p.lo) return 0;  // nothing to move
+  if (off < 0 || off + p.lo < 0 || off + p.hi > r.bytes) throw std::out_of_range(outside);
+  if (!r.ptr) throw std::runtime_error("mpit: target window not mapped on this rank");
+  return reinterpret_cast<uintptr_t>(r.ptr) + uintptr_t(off);
+}
+
 void Window::copy_plan(int dir, int m, int64_t off, const CopyPlan& p, uintptr_t packed, hipStream_t s) {
   const Remote& r = remote_.at(size_t(m));
-  const char* what = dir ? "mpit: Put outside the target window" : "mpit: Get outside the target window";
-  if (p.lo > p.hi) throw std::invalid_argument("mpit: one-sided plan with lo > hi");
-  if (p.hi == p.lo) return;  // nothing to move
-  if (off < 0 || off + p.lo < 0 || off + p.hi > r.bytes) throw std::out_of_range(what);
-  if (!r.ptr) throw std::runtime_error("mpit: target window not mapped on this rank");
-  const uintptr_t strided = reinterpret_cast<uintptr_t>(r.ptr) + uintptr_t(off);
+  const uintptr_t strided =
+      plan_base(m, off, p, dir ? "mpit: Put outside the target window" : "mpit: Get outside the target window");
+  if (!strided) return;
   if (r.device) {
     if (eng_.device() < 0) throw std::runtime_error("mpit: device target window on a rank without a device");
     type_copy(eng_.device(), s, dir, strided, packed, p.loops, p.table, p.R, p.L, p.per, p.unit);
@@ -235,6 +241,52 @@ void Window::accumulate(int m, int64_t off, uintptr_t src, bool src_dev, int64_t
     } else {
       if (src_dev) throw std::invalid_argument("mpit: Accumulate into a host window needs a host origin buffer");
       ew_update(kAxpby, 0, -1, nullptr, nelem, {reinterpret_cast<uintptr_t>(dst), src}, bf, {a, b});
+    }
+  } catch (...) {
+    unlock(m);
+    throw;
+  }
+  unlock(m);
+}
+
+namespace {
+// whether `p` is device memory, asked of the runtime (only on a rank that has a device; plain
+// host memory is unknown to it, which is an error there and not one here)
+bool device_memory(uintptr_t p) {
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, reinterpret_cast<const void*>(p)) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return at.type == hipMemoryTypeDevice;
+}
+}  // namespace
+
+void Window::accumulate_plan(int m, int64_t off, const CopyPlan& p, int op, int dtype, uintptr_t packed,
+                             uintptr_t fetch, hipStream_t s) {
+  const Remote& r = remote_.at(size_t(m));
+  const uintptr_t strided = plan_base(m, off, p, "mpit: Accumulate outside the target window");
+  if (!strided) return;
+  if (!type_accumulate_supported(op, dtype)) throw std::invalid_argument("mpit: Accumulate: unsupported (op, dtype)");
+  if (r.device && eng_.device() < 0) throw std::runtime_error("mpit: device target window on a rank without a device");
+  if (eng_.device() >= 0) {
+    hipw(hipSetDevice(eng_.device()), "hipSetDevice");
+    for (uintptr_t q : {packed, fetch}) {
+      if (!q) continue;
+      const bool dev = device_memory(q);
+      if (r.device && !dev)
+        throw std::invalid_argument("mpit: Accumulate into a device window needs device origin and result buffers");
+      if (!r.device && dev)
+        throw std::invalid_argument("mpit: Accumulate into a host window needs host origin and result buffers");
+    }
+  }
+  lock(m, true);
+  try {
+    if (r.device) {
+      type_accumulate(eng_.device(), s, op, dtype, strided, packed, fetch, p.loops, p.table, p.R, p.L, p.per, p.unit);
+      hipw(hipStreamSynchronize(s), "Accumulate sync");
+    } else {
+      type_accumulate(-1, nullptr, op, dtype, strided, packed, fetch, p.loops, p.table, p.R, p.L, p.per, p.unit);
     }
   } catch (...) {
     unlock(m);

@@ -78,6 +78,16 @@ class Window {
   // through the exclusive lock of the target.
   void accumulate(int m, int64_t off, uintptr_t src, bool src_dev, int64_t nelem, bool bf16, float a, float b,
                   hipStream_t s);
+  // Accumulate / Get_accumulate over a whole target layout in one type_accumulate launch
+  // (kernels.h): for every element of the layout `p` at byte offset `off` of member m's window,
+  // target = comb(op, target, packed) and, with fetch != 0, fetch = the target's previous element.
+  // op: PeerOp / AccOp, dtype: PeerDtype. The plan's span is checked against the target window
+  // as put_plan does (std::out_of_range, nothing launched, no lock taken). One exclusive target
+  // lock, one launch on s (the host twin for a host window), one stream synchronise, unlock (on
+  // a throw too): atomic w.r.t. other accumulates and complete on return. `packed` / `fetch` are
+  // device memory for a device target and host memory for a host target.
+  void accumulate_plan(int m, int64_t off, const CopyPlan& p, int op, int dtype, uintptr_t packed, uintptr_t fetch,
+                       hipStream_t s);
   void lock(int m, bool exclusive);
   bool try_lock(int m, bool exclusive);
   void unlock(int m);
@@ -122,6 +132,8 @@ class Window {
   };
   std::vector<Remote> remote_;
   std::vector<int> held_;  // lock mode held per member: 0 none, 1 shared, 2 exclusive
+  // the span check of a plan against member m's window; the strided base address, 0 for an empty plan
+  uintptr_t plan_base(int m, int64_t off, const CopyPlan& p, const char* outside) const;
   void copy_plan(int dir, int m, int64_t off, const CopyPlan& p, uintptr_t packed, hipStream_t s);
   void* ar_tmp_ = nullptr;  // one-shot in place: the private result, copied back after B2
   int64_t ar_tmp_bytes_ = 0;

@@ -24,6 +24,7 @@
 
 #include "ew.h"
 #include "kernels.h"
+#include "peer_ops.h"  // the element tags, widen / narrow / comb (shared with type_acc.hip)
 
 // plain IEEE operations in the stated order: no contraction anywhere in this file
 #pragma clang fp contract(off)
@@ -39,52 +40,6 @@ struct PeerTable {
   uint64_t dst[kPeerMax];
   int32_t ns, nd;
 };
-
-// element tags: S storage type, A accumulator type
-struct TF32 { using S = float; using A = float; static constexpr bool kInt = false; };
-struct TBf16 { using S = uint16_t; using A = float; static constexpr bool kInt = false; };
-struct TF16 { using S = uint16_t; using A = float; static constexpr bool kInt = false; };
-struct TF64 { using S = double; using A = double; static constexpr bool kInt = false; };
-struct TI32 { using S = int32_t; using A = int32_t; using U = uint32_t; static constexpr bool kInt = true; };
-struct TI64 { using S = int64_t; using A = int64_t; using U = uint64_t; static constexpr bool kInt = true; };
-struct TU8 { using S = uint8_t; using A = uint8_t; using U = uint8_t; static constexpr bool kInt = true; };
-
-template <class Tag>
-MPIT_HD typename Tag::A widen(typename Tag::S v) {
-  if constexpr (std::is_same_v<Tag, TBf16>) return bf2f(v);
-  else if constexpr (std::is_same_v<Tag, TF16>) return float(__builtin_bit_cast(_Float16, v));
-  else return v;
-}
-template <class Tag>
-MPIT_HD typename Tag::S narrow(typename Tag::A v) {
-  if constexpr (std::is_same_v<Tag, TBf16>) return f2bf(v);
-  else if constexpr (std::is_same_v<Tag, TF16>) return __builtin_bit_cast(uint16_t, static_cast<_Float16>(v));
-  else return v;
-}
-
-template <class Tag, int OP>
-MPIT_HD typename Tag::A comb(typename Tag::A a, typename Tag::A b) {
-  using A = typename Tag::A;
-  if constexpr (OP == kPrLand) return A((a != A(0)) && (b != A(0)) ? 1 : 0);
-  else if constexpr (OP == kPrLor) return A((a != A(0)) || (b != A(0)) ? 1 : 0);
-  else if constexpr (OP == kPrLxor) return A((a != A(0)) != (b != A(0)) ? 1 : 0);
-  else if constexpr (Tag::kInt) {
-    using U = typename Tag::U;  // wrap-around like torch, without signed overflow
-    if constexpr (OP == kPrSum) return A(U(U(a) + U(b)));
-    else if constexpr (OP == kPrProd) return A(U(U(a) * U(b)));
-    else if constexpr (OP == kPrMax) return a > b ? a : b;
-    else if constexpr (OP == kPrMin) return a < b ? a : b;
-    else if constexpr (OP == kPrBand) return A(a & b);
-    else if constexpr (OP == kPrBor) return A(a | b);
-    else return A(a ^ b);
-  } else {
-    if constexpr (OP == kPrSum) return a + b;
-    else if constexpr (OP == kPrProd) return a * b;
-    else if constexpr (OP == kPrMax) return (a != a) ? a : ((b != b) ? b : (a > b ? a : b));  // NaN propagates
-    else if constexpr (OP == kPrMin) return (a != a) ? a : ((b != b) ? b : (a < b ? a : b));
-    else return a;  // bitwise ops on floats: peer_reduce_supported says no
-  }
-}
 
 // x[0][e] = x[0][e] op x[1][e] op ... op x[ns-1][e]
 template <class Tag, int OP, int NS, int VE>

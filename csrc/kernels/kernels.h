@@ -412,4 +412,24 @@ void type_copy(int dev, hipStream_t s, int dir, uintptr_t strided, uintptr_t pac
                const std::vector<std::array<int64_t, 2>>& loops, uintptr_t table, int64_t R, int64_t L, int64_t per,
                int unit, int max_blocks = 0, bool wide = false);
 
+// ---- one-sided accumulate on a derived-datatype layout (type_acc.hip) --------------------
+// For every element e of the layout (type_copy's: loops, table, R, L, per, unit; the same run
+// modes, index widths, max_blocks and wide), in one launch on `s`, or the host twin for dev < 0:
+//     old = strided[e];  strided[e] = comb(op, old, packed[e]);  fetch[e] = old   (fetch != 0)
+// a = the target element, b = the origin element, comb / widen / narrow those of peer_reduce:
+// the same operands give the same bits as the all-reduce. op: a PeerOp, kAccReplace (store the
+// origin element) or kAccNoOp (store nothing: only meaningful with a fetch stream; packed may
+// be 0). dtype: a PeerDtype. `packed` and `fetch` are contiguous streams of the layout's packed
+// size. One item is `unit` bytes = unit / sizeof(element) elements: std::invalid_argument when
+// unit < sizeof(element), for an unsupported (op, dtype) (type_accumulate_supported: the ten of
+// peer_reduce_supported, REPLACE and NO_OP on all seven types) and for what type_copy refuses,
+// before any launch. No atomics: the caller holds the target's exclusive lock. The layout is
+// trusted; overlapping target runs are erroneous (as for MPI_Accumulate) and undefined here.
+// Allocates and synchronises nothing.
+enum AccOp : int { kAccReplace = kPrOps, kAccNoOp, kAccOps };
+bool type_accumulate_supported(int op, int dtype);
+void type_accumulate(int dev, hipStream_t s, int op, int dtype, uintptr_t strided, uintptr_t packed, uintptr_t fetch,
+                     const std::vector<std::array<int64_t, 2>>& loops, uintptr_t table, int64_t R, int64_t L,
+                     int64_t per, int unit, int max_blocks = 0, bool wide = false);
+
 }  // namespace mpit

@@ -21,8 +21,10 @@ import torch
 
 # which path moved the bytes: `kernel` = type_copy launches (pack / unpack / send / recv and
 # the packing of a derived one-sided origin), `index` = the byte-index fallback, `rma_kernel` =
-# one-launch Put / Get on a derived target type, `rma_copies` = per-run peer copies
-COUNTERS = {"kernel": 0, "index": 0, "rma_kernel": 0, "rma_copies": 0}
+# one-launch Put / Get on a derived target type, `rma_copies` = per-run peer copies,
+# `rma_acc_kernel` = one-launch Accumulate / Get_accumulate calls (type_accumulate),
+# `rma_acc_runs` = per-run axpby accumulates of the fallback path
+COUNTERS = {"kernel": 0, "index": 0, "rma_kernel": 0, "rma_copies": 0, "rma_acc_kernel": 0, "rma_acc_runs": 0}
 
 _BASIC: Dict[str, Tuple[int, Optional[torch.dtype]]] = {
     "CHAR": (1, torch.int8), "BYTE": (1, torch.uint8), "SHORT": (2, torch.int16), "INT": (4, torch.int32),
@@ -250,6 +252,7 @@ class Datatype:
         self._fold_cache = None  # the folded instance layout (plan)
         self._plan_cache = {}  # count -> Plan
         self._tab_cache = {}  # device -> uploaded run table, shared by the plans of every count
+        self._elem_cache = None  # (type-map length, element_dtype())
 
     # ---------------------------------------------------------------- queries
     def Get_size(self) -> int:
@@ -454,8 +457,11 @@ class Datatype:
 
     def element_dtype(self) -> Optional[torch.dtype]:
         """The one basic torch dtype every entry of the type map has (None: mixed / none)."""
-        kinds = {b for _, b in self.typemap if _BASIC[b][0]}
-        return _BASIC[kinds.pop()][1] if len(kinds) == 1 else None
+        key = len(self.typemap)  # walked once per type, not once per one-sided call
+        if self._elem_cache is None or self._elem_cache[0] != key:
+            kinds = {b for _, b in self.typemap if _BASIC[b][0]}
+            self._elem_cache = (key, _BASIC[kinds.pop()][1] if len(kinds) == 1 else None)
+        return self._elem_cache[1]
 
     def __repr__(self):
         return f"Datatype({self._name or self.envelope[0]}, size={self.Get_size()}, extent={self.extent})"

@@ -35,6 +35,7 @@ from .parallel.ps import (tag_ps_recv_grad, tag_ps_recv_grad_tail, tag_ps_recv_h
                           tag_ps_recv_param, tag_ps_recv_param_tail, tag_ps_recv_stop, tag_ps_send_param)
 from .utils.serialize import deserialize, serialize  # noqa: F401
 from .window import LOCK_EXCLUSIVE, LOCK_SHARED, Win  # noqa: F401
+from .window import acc_codes as _acc_codes, acc_unavailable as _acc_unavailable, contiguous_plan as _contiguous_plan
 
 SUCCESS = 0
 # ---------------------------------------------------------------- constants (lua-mpi.h:125-231)
@@ -42,7 +43,7 @@ from .datatypes import (BYTE, CHAR, DOUBLE, DOUBLE_INT, FLOAT, FLOAT_INT, INT, L
                         LONG_DOUBLE_INT, LONG_INT, LONG_LONG_INT, PACKED, SHORT, SHORT_INT, TWOINT, UB, UNSIGNED,
                         UNSIGNED_CHAR, UNSIGNED_LONG, UNSIGNED_SHORT)
 from .comm import (ANY_SOURCE, ANY_TAG, BAND, BOR, BXOR, CONGRUENT, IDENT, LAND, LOR, LXOR, MAX, MAXLOC, MIN,  # noqa: E402,F401
-                   MINLOC, PROC_NULL, PROD, ROOT, SIMILAR, SUM, UNDEFINED, UNEQUAL)
+                   MINLOC, NO_OP, PROC_NULL, PROD, REPLACE, ROOT, SIMILAR, SUM, UNDEFINED, UNEQUAL)
 from .misc import (ERR_ARG, ERR_BUFFER, ERR_COMM, ERR_COUNT, ERR_DIMS, ERR_GROUP, ERR_IN_STATUS,  # noqa: E402,F401
                    ERR_INTERN, ERR_LASTCODE, ERR_OP, ERR_OTHER, ERR_PENDING, ERR_RANK, ERR_REQUEST, ERR_ROOT,
                    ERR_TAG, ERR_TOPOLOGY, ERR_TRUNCATE, ERR_TYPE, ERR_UNKNOWN, KEYVAL_INVALID)
@@ -529,16 +530,65 @@ def Get(origin, origin_count, origin_type, target_rank, target_disp, target_coun
     return SUCCESS
 
 
+def _acc_plan(target_count, target_type, win):
+    """The layout plan an accumulate walks over the target (count, datatype): the type's plan for
+    a derived type, one contiguous run for a basic one. None for a negative displacement."""
+    if target_type is None or target_type.is_contiguous_basic():
+        size = target_type.Get_size() if target_type is not None else win.tensor.element_size()
+        return _contiguous_plan(size * int(target_count))
+    plan = target_type.plan(target_count)
+    return plan if plan.lo >= 0 else None
+
+
+def _acc_kernel(what, data, result, edt, target_rank, target_disp, target_count, target_type, op, win):
+    """Accumulate `data` (the origin's packed stream, None with NO_OP) onto the target layout in
+    one type_accumulate launch, the target's previous elements fetched into `result` (a packed
+    uint8 stream on any side, None: no fetch). True when done; a string, the reason, with nothing
+    locked or launched, when this path does not serve the call."""
+    tdt = target_type.element_dtype() if target_type is not None else win.tensor.dtype
+    if tdt != edt:
+        return f"elements of one type are needed on every side (origin / result {edt}, target {tdt})"
+    codes = _acc_codes(what, op, edt)  # TypeError for an op of the kernel's on a type it lacks
+    if codes is None:
+        return _acc_unavailable(op)
+    es = torch.empty(0, dtype=edt).element_size()
+    plan = _acc_plan(target_count, target_type, win)
+    if plan is None:
+        return "the target datatype has a negative displacement"
+    for stream in (data, result):
+        if stream is not None and stream.numel() != plan.total:
+            raise ValueError(f"one-sided: origin / result carries {stream.numel()} bytes, target (count "
+                             f"{target_count}, {target_type}) {plan.total}")
+    like = data if data is not None else result
+    side = _window_side(win, target_rank, like)
+    packed = data.to(side) if data is not None else None
+    land = result
+    if result is not None and result.device.type != side.type:
+        land = torch.empty_like(result, device=side)
+    if not win._plan_acc(packed, land, target_rank, int(target_disp) * win.disp_unit, plan, codes, es):
+        return "the target address or a buffer is not aligned to the element size"
+    _dt.COUNTERS["rma_acc_kernel"] += 1
+    if land is not result:  # the call is complete: cross the bus
+        result.copy_(land)
+    return True
+
+
 def Accumulate(origin, origin_count, origin_type, target_rank, target_disp, target_count, target_type, op, win):
-    """MPI_Accumulate (mpifuncs.c:9): SUM / REPLACE of fp32 / bf16 elements, per contiguous
-    run of the target datatype; both type maps must hold that one element type."""
+    """MPI_Accumulate (mpifuncs.c:9): target = op(target, origin) element by element over the
+    target datatype's layout; both type maps must hold one element type. Every predefined
+    reduction, REPLACE and NO_OP on fp32 / bf16 / fp16 / fp64 / int32 / int64 / uint8 run as one
+    type_accumulate launch under one target lock, basic and derived targets alike. The fallback
+    (MPIT_DTYPE_KERNEL=0, a negative displacement, an address not aligned to the element): SUM /
+    REPLACE of fp32 / bf16, one axpby launch per contiguous run of the target datatype."""
     from .comm import REPLACE, SUM
 
     data, edt = _origin_stream(origin, origin_count, origin_type)
+    op = op or SUM
+    if _acc_kernel("Accumulate", data, None, edt, target_rank, target_disp, target_count, target_type, op, win) is True:
+        return SUCCESS
     tdt = target_type.element_dtype() if target_type is not None else win.tensor.dtype
     if edt not in (torch.float32, torch.bfloat16) or tdt != edt:
         raise TypeError(f"Accumulate: fp32 / bf16 elements of one type on both sides (origin {edt}, target {tdt})")
-    op = op or SUM
     if op is SUM:
         a, b = 1.0, 1.0
     elif op is REPLACE:
@@ -552,6 +602,48 @@ def Accumulate(origin, origin_count, origin_type, target_rank, target_disp, targ
         win._acc_elems(vals[pos // es:(pos + n) // es], target_rank, off, a, b)
         pos += n
     return SUCCESS
+
+
+def Get_accumulate(origin, origin_count, origin_type, result, result_count, result_type, target_rank, target_disp,
+                   target_count, target_type, op, win):
+    """MPI_Get_accumulate: result = target, then target = op(target, origin), element by element
+    over the target datatype's layout, in the one type_accumulate launch of Accumulate with a
+    fetch stream. Blocking: the result, unpacked by `result_type`, is complete on return. With
+    NO_OP the origin may be None (an atomic Get). There is no per-run fallback: where the kernel
+    path does not serve the call this raises with the reason."""
+    from .comm import NO_OP, SUM
+
+    op = op or SUM
+    if origin is None:
+        if op is not NO_OP:
+            raise ValueError("Get_accumulate: only NO_OP goes without an origin buffer")
+        data = None
+    else:
+        data, edt = _origin_stream(origin, origin_count, origin_type)
+    derived = not (result_type is None or result_type.is_contiguous_basic())
+    if not derived:
+        if not result.is_contiguous():
+            raise ValueError("Get_accumulate: contiguous result buffer needed for a basic datatype")
+        es = result_type.Get_size() if result_type is not None else result.element_size()
+        raw = result.reshape(-1).view(torch.uint8)
+        if int(result_count) * es > raw.numel():
+            raise ValueError(f"Get_accumulate: {result_count} elements exceed the result buffer")
+        stage, rdt = raw[:int(result_count) * es], result.dtype
+    else:
+        stage, rdt = result_type.staging(result, result_count), result_type.element_dtype()
+    if data is not None and edt != rdt:
+        raise TypeError(f"Get_accumulate: elements of one type on every side (origin {edt}, result {rdt})")
+    done = _acc_kernel("Get_accumulate", data, stage, rdt, target_rank, target_disp, target_count, target_type, op, win)
+    if done is not True:
+        raise ValueError(f"Get_accumulate: {done}")
+    if derived:  # a basic result was written in place
+        result_type.unpack(stage, result, int(result_count))
+    return SUCCESS
+
+
+def Fetch_and_op(origin, result, datatype, target_rank, target_disp, op, win):
+    """MPI_Fetch_and_op: Get_accumulate of one element of `datatype`."""
+    return Get_accumulate(origin, 1, datatype, result, 1, datatype, target_rank, target_disp, 1, datatype, op, win)
 
 
 Win_fence = lambda assertion, win: win.Fence(assertion)  # noqa: E731

@@ -16,8 +16,10 @@ import ctypes
 import weakref
 from typing import Optional
 
+import numpy as np
 import torch
 
+from . import datatypes as _dt
 from . import runtime as _rt
 from ._ext import native
 
@@ -42,6 +44,48 @@ def host_view(ptr: int, nbytes: int, dtype: torch.dtype) -> torch.Tensor:
         return torch.empty(0, dtype=dtype)
     buf = (ctypes.c_uint8 * nbytes).from_address(ptr)
     return torch.frombuffer(buf, dtype=dtype)
+
+
+ACC_REPLACE, ACC_NO_OP = 10, 11  # csrc/kernels/kernels.h AccOp, after the ten PeerOp codes
+
+_contig_plans = {}
+
+
+def contiguous_plan(nbytes: int):
+    """The one-run layout plan of `nbytes` contiguous bytes (a basic target of an accumulate)."""
+    p = _contig_plans.get(nbytes)
+    if p is None:
+        if len(_contig_plans) >= 256:
+            _contig_plans.clear()
+        lens = np.array([nbytes] if nbytes > 0 else [], dtype=np.int64)
+        p = _contig_plans[nbytes] = _dt.Plan((), np.zeros(len(lens), dtype=np.int64), lens)
+    return p
+
+
+def acc_unavailable(op) -> str:
+    """Why the one-launch accumulate does not serve `op` (acc_codes gave None)."""
+    if not _dt.kernel_enabled():
+        return "the type_accumulate kernel is switched off (MPIT_DTYPE_KERNEL=0) or the native module did not load"
+    return f"{op!r} is not a predefined reduction, REPLACE or NO_OP"
+
+
+def acc_codes(what: str, op, dtype):
+    """(op, dtype) codes of type_accumulate, or None when the kernel is off or `op` is not one of
+    its twelve (the caller falls back or refuses). TypeError, naming both, for one of its ops on
+    an element type it does not have: a float bitwise op, a type outside the seven."""
+    from .comm import _PR_DTYPES, _PR_OP_CODE, NO_OP, REPLACE
+
+    if not _dt.kernel_enabled():
+        return None
+    code = _PR_OP_CODE.get(op)
+    if code is None:
+        code = ACC_REPLACE if op is REPLACE else (ACC_NO_OP if op is NO_OP else None)
+    if code is None:
+        return None
+    dc = _PR_DTYPES.get(dtype)
+    if dc is None or not native().type_accumulate_supported(code, dc):
+        raise TypeError(f"{what}: {op.name} is not supported on {dtype} elements")
+    return code, dc
 
 
 class Win:
@@ -125,12 +169,19 @@ class Win:
                     origin.numel() * origin.element_size(), self._stream())
 
     def Accumulate(self, origin: torch.Tensor, target_rank: int, target_disp: int = 0, op=None):
-        """target += origin (SUM) or target = origin (REPLACE); fp32/bf16. Atomic with
-        respect to other Accumulates on the same target (exclusive target lock)."""
+        """target = op(target, origin) element by element: every predefined reduction, REPLACE and
+        NO_OP on fp32 / bf16 / fp16 / fp64 / int32 / int64 / uint8 in one type_accumulate launch
+        (with MPIT_DTYPE_KERNEL=0: SUM / REPLACE on fp32 / bf16 through the axpby kernel). Atomic
+        with respect to other Accumulates on the same target (exclusive target lock); blocking."""
         from .comm import REPLACE, SUM
 
         op = op or SUM
         o = origin.contiguous().reshape(-1)
+        codes = acc_codes("Accumulate", op, o.dtype)
+        if codes is not None and self._plan_acc(o, None, target_rank, target_disp * self.disp_unit,
+                                                contiguous_plan(o.numel() * o.element_size()), codes, o.element_size()):
+            _dt.COUNTERS["rma_acc_kernel"] += 1
+            return
         if o.dtype not in (torch.float32, torch.bfloat16):
             raise TypeError("Accumulate supports float32 / bfloat16")
         if op is SUM:
@@ -141,6 +192,42 @@ class Win:
             raise ValueError("Accumulate supports SUM and REPLACE")
         self._w.accumulate(target_rank, target_disp * self.disp_unit, o.data_ptr(), o.is_cuda, o.numel(),
                            o.dtype == torch.bfloat16, a, b, self._stream())
+        _dt.COUNTERS["rma_acc_runs"] += 1
+
+    def Get_accumulate(self, origin: Optional[torch.Tensor], result: torch.Tensor, target_rank: int,
+                       target_disp: int = 0, op=None):
+        """result = target, then target = op(target, origin), element by element in one launch
+        under the target's exclusive lock; complete on return. With NO_OP the origin may be None
+        (an atomic Get). `result` is contiguous, of the target's element type and on the target
+        window's side, like the origin."""
+        from .comm import NO_OP, SUM
+
+        op = op or SUM
+        if not result.is_contiguous():
+            raise ValueError("Get_accumulate needs a contiguous result buffer")
+        if origin is None:
+            if op is not NO_OP:
+                raise ValueError("Get_accumulate: only NO_OP goes without an origin buffer")
+            o = None
+        else:
+            o = origin.contiguous().reshape(-1)
+            if o.dtype != result.dtype or o.numel() != result.numel():
+                raise ValueError("Get_accumulate: origin and result hold the same elements")
+        codes = acc_codes("Get_accumulate", op, result.dtype)
+        if codes is None:
+            raise ValueError(f"Get_accumulate: {acc_unavailable(op)}")
+        es = result.element_size()
+        if not self._plan_acc(o, result.reshape(-1), target_rank, target_disp * self.disp_unit,
+                              contiguous_plan(result.numel() * es), codes, es):
+            raise ValueError("Get_accumulate: a buffer or the target is not aligned to the element size")
+        _dt.COUNTERS["rma_acc_kernel"] += 1
+
+    def Fetch_and_op(self, origin: Optional[torch.Tensor], result: torch.Tensor, target_rank: int,
+                     target_disp: int = 0, op=None):
+        """Get_accumulate of one element (MPI_Fetch_and_op): counters, tickets, work queues."""
+        if result.numel() != 1 or (origin is not None and origin.numel() != 1):
+            raise ValueError("Fetch_and_op moves exactly one element")
+        self.Get_accumulate(origin, result, target_rank, target_disp, op)
 
     # byte-addressed forms (the datatype-faithful Put / Get / Accumulate of mpiT.py): one
     # copy / accumulate per contiguous run of the target datatype
@@ -175,11 +262,44 @@ class Win:
                            data.dtype == torch.bfloat16, a, b, self._stream())
         self._keep_all = getattr(self, "_keep_all", [])
         self._keep_all.append(data)
+        _dt.COUNTERS["rma_acc_runs"] += 1
+
+    # the accumulate of a whole target layout (datatypes.Plan) in ONE type_accumulate launch under
+    # one exclusive target lock: `data` the origin's packed stream (None with NO_OP), `fetch` the
+    # stream that receives the target's previous elements (None: no fetch), both contiguous and
+    # on the window's side; codes = acc_codes(...), es the element size. Blocking: complete on
+    # return. False, with nothing locked or launched, when an address makes the item smaller
+    # than an element (the caller falls back or refuses).
+    def _plan_acc(self, data: Optional[torch.Tensor], fetch: Optional[torch.Tensor], target_rank: int, byte_disp: int,
+                  plan, codes, es: int) -> bool:
+        if plan.total == 0:
+            return True
+        side = self._w.remote_device(target_rank)
+        for t in (data, fetch):
+            if t is not None and (t.is_cuda != side or not t.is_contiguous()):
+                raise ValueError("one-sided accumulate: contiguous origin and result streams on the target window's "
+                                 "side are needed")
+        tab, off, table = plan.table((data if data is not None else fetch).device)
+        base = int(byte_disp) + off
+        pp = data.data_ptr() if data is not None else 0
+        fp = fetch.data_ptr() if fetch is not None else 0
+        unit = plan.unit(self._w.remote_ptr(target_rank) + base, pp | fp)
+        if unit < es:
+            return False
+        self._w.accumulate_plan(target_rank, base, plan._loops, tab, plan.R, plan.L, plan.per, unit, plan.lo - off,
+                                plan.hi - off, codes[0], codes[1], pp, fp, self._stream())
+        return True
 
     def Raccumulate(self, *a, **k):
         from .comm import Request
 
         self.Accumulate(*a, **k)
+        return Request(self.comm)
+
+    def Rget_accumulate(self, *a, **k):
+        from .comm import Request
+
+        self.Get_accumulate(*a, **k)
         return Request(self.comm)
 
     def Rput(self, *a, **k):
