@@ -628,7 +628,47 @@ PYBIND11_MODULE(_mpit, m) {
              return w.allreduce(off, nelem, dtype, op, S(s), mode, dst);
            },
            py::arg("off"), py::arg("nelem"), py::arg("dtype"), py::arg("op"), py::arg("stream"), py::arg("mode") = 0,
-           py::arg("dst") = 0, py::call_guard<py::gil_scoped_release>());
+           py::arg("dst") = 0, py::call_guard<py::gil_scoped_release>())
+      // segs: [(member, byte offset in that member's window, local destination, bytes)]
+      .def("pull_gather",
+           [](Window& w, const std::vector<std::tuple<int, int64_t, uintptr_t, int64_t>>& segs, uintptr_t s) {
+             std::vector<Window::PullSeg> v;
+             for (const auto& g : segs) v.push_back({std::get<0>(g), std::get<1>(g), std::get<2>(g), std::get<3>(g)});
+             return w.pull_gather(v, S(s));
+           },
+           py::arg("segs"), py::arg("stream"), py::call_guard<py::gil_scoped_release>())
+      .def("pull_fold",
+           [](Window& w, int64_t off, int64_t nelem, int dtype, int op, uintptr_t dst, int m0, int m1, uintptr_t s) {
+             return w.pull_fold(off, nelem, dtype, op, dst, m0, m1, S(s));
+           },
+           py::arg("off"), py::arg("nelem"), py::arg("dtype"), py::arg("op"), py::arg("dst"), py::arg("m0"),
+           py::arg("m1"), py::arg("stream"), py::call_guard<py::gil_scoped_release>())
+      .def("scan",
+           [](Window& w, int64_t off, int64_t nelem, int dtype, int op, bool exclusive, uintptr_t s) {
+             return w.scan(off, nelem, dtype, op, exclusive, S(s));
+           },
+           py::arg("off"), py::arg("nelem"), py::arg("dtype"), py::arg("op"), py::arg("exclusive"), py::arg("stream"),
+           py::call_guard<py::gil_scoped_release>());
+  m.def(
+      "peer_gather",
+      [](int dev, uintptr_t s, std::vector<uintptr_t> srcs, std::vector<uintptr_t> dsts, std::vector<int64_t> bytes,
+         int max_blocks) { peer_gather(dev, S(s), srcs, dsts, bytes, max_blocks); },
+      py::arg("dev"), py::arg("stream"), py::arg("srcs"), py::arg("dsts"), py::arg("bytes"), py::arg("max_blocks") = 0,
+      py::call_guard<py::gil_scoped_release>());
+  m.def(
+      "peer_fold",
+      [](int dev, uintptr_t s, int op, int dtype, std::vector<uintptr_t> srcs, uintptr_t dst, int64_t n,
+         int max_blocks) { peer_fold(dev, S(s), op, dtype, srcs, dst, n, max_blocks); },
+      py::arg("dev"), py::arg("stream"), py::arg("op"), py::arg("dtype"), py::arg("srcs"), py::arg("dst"), py::arg("n"),
+      py::arg("max_blocks") = 0, py::call_guard<py::gil_scoped_release>());
+  m.def(
+      "peer_scan",
+      [](int dev, uintptr_t s, int op, int dtype, bool exclusive, std::vector<uintptr_t> srcs,
+         std::vector<uintptr_t> dsts, int64_t n, int max_blocks) {
+        peer_scan(dev, S(s), op, dtype, exclusive, srcs, dsts, n, max_blocks);
+      },
+      py::arg("dev"), py::arg("stream"), py::arg("op"), py::arg("dtype"), py::arg("exclusive"), py::arg("srcs"),
+      py::arg("dsts"), py::arg("n"), py::arg("max_blocks") = 0, py::call_guard<py::gil_scoped_release>());
   m.def("peer_reduce_supported", &peer_reduce_supported, py::arg("op"), py::arg("dtype"));
   m.def(
       "peer_reduce",

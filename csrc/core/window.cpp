@@ -453,4 +453,107 @@ bool Window::allreduce(int64_t off, int64_t nelem, int dtype, int op, hipStream_
   return true;
 }
 
+int Window::self_member() const {
+  for (size_t m = 0; m < remote_.size(); ++m)
+    if (remote_[m].ctl == ctl_) return int(m);
+  throw std::runtime_error("mpit: window collective on a rank that is no member");
+}
+
+bool Window::pull_gather(const std::vector<PullSeg>& segs, hipStream_t s) {
+  if (!allreduce_capable()) return false;
+  if (segs.size() > size_t(kPeerMax)) throw std::invalid_argument("mpit: pull-gather takes up to 8 segments");
+  const int dev = device_ ? eng_.device() : -1;
+  self_member();
+  std::vector<uintptr_t> srcs, dsts;
+  std::vector<int64_t> bytes;
+  for (const PullSeg& g : segs) {
+    if (g.member < 0 || g.member >= int(remote_.size())) throw std::out_of_range("mpit: pull-gather member out of range");
+    const Remote& r = remote_[size_t(g.member)];
+    if (g.off < 0 || g.bytes < 0 || g.off + g.bytes > r.bytes)
+      throw std::out_of_range("mpit: pull-gather range outside a member's window");
+    if (g.bytes == 0) continue;
+    if (!g.dst) throw std::invalid_argument("mpit: pull-gather without a destination");
+    srcs.push_back(reinterpret_cast<uintptr_t>(r.ptr) + uintptr_t(g.off));
+    dsts.push_back(g.dst);
+    bytes.push_back(g.bytes);
+  }
+  auto drain = [&](const char* what) {
+    if (dev >= 0) hipw(hipStreamSynchronize(s), what);
+  };
+  if (dev >= 0) hipw(hipSetDevice(dev), "hipSetDevice");
+  drain("pull-gather B1");
+  sync();  // B1: every member's source is complete
+  if (!srcs.empty()) peer_gather(dev, s, srcs, dsts, bytes);
+  drain("pull-gather B2");
+  sync();  // B2: every read of my window is finished
+  return true;
+}
+
+bool Window::pull_fold(int64_t off, int64_t nelem, int dtype, int op, uintptr_t dst, int m0, int m1, hipStream_t s) {
+  if (!allreduce_capable() || !peer_reduce_supported(op, dtype)) return false;
+  const int64_t es = peer_dtype_size(dtype);
+  const int n = int(remote_.size());
+  if (off < 0 || nelem < 0 || off % es) throw std::invalid_argument("mpit: pull-fold range misaligned");
+  if (m0 < 0 || m1 > n || m0 >= m1) throw std::out_of_range("mpit: pull-fold member range");
+  if (dst % uintptr_t(es)) throw std::invalid_argument("mpit: pull-fold destination misaligned");
+  const int dev = device_ ? eng_.device() : -1;
+  self_member();
+  std::vector<uintptr_t> srcs;
+  if (dst && nelem > 0) {
+    for (int m = m0; m < m1; ++m) {
+      if (off + nelem * es > remote_[size_t(m)].bytes)
+        throw std::out_of_range("mpit: pull-fold range outside a member's window");
+      srcs.push_back(reinterpret_cast<uintptr_t>(remote_[size_t(m)].ptr) + uintptr_t(off));
+    }
+  }
+  auto drain = [&](const char* what) {
+    if (dev >= 0) hipw(hipStreamSynchronize(s), what);
+  };
+  if (dev >= 0) hipw(hipSetDevice(dev), "hipSetDevice");
+  drain("pull-fold B1");
+  sync();  // B1: every member's input is complete
+  if (!srcs.empty()) peer_fold(dev, s, op, dtype, srcs, dst, nelem);
+  drain("pull-fold B2");
+  sync();  // B2: every read of my window is finished
+  return true;
+}
+
+bool Window::scan(int64_t off, int64_t nelem, int dtype, int op, bool exclusive, hipStream_t s) {
+  if (!allreduce_capable() || !peer_reduce_supported(op, dtype)) return false;
+  const int64_t es = peer_dtype_size(dtype);
+  const int n = int(remote_.size());
+  if (off < 0 || nelem < 0 || off % es) throw std::invalid_argument("mpit: window scan range misaligned");
+  for (const Remote& r : remote_)
+    if (off + nelem * es > r.bytes) throw std::out_of_range("mpit: scan range outside a member's window");
+  const int dev = device_ ? eng_.device() : -1;
+  const int me = self_member();
+  auto drain = [&](const char* what) {
+    if (dev >= 0) hipw(hipStreamSynchronize(s), what);
+  };
+  if (dev >= 0) hipw(hipSetDevice(dev), "hipSetDevice");
+  drain("scan B1");
+  sync();  // B1: every member's input is complete
+  if (nelem > 0) {
+    // the slices of Window::allreduce's two-shot: interior bounds rounded down to a 16-B address
+    // of member 0's range, from the alignment member 0 published (the same on every rank)
+    auto bound = [&](int k) -> int64_t {
+      if (k <= 0) return 0;
+      if (k >= n) return nelem;
+      const int64_t b = nelem * k / n;
+      const int64_t a = ((int64_t(remote_[0].align) + off + b * es) & 15) / es;
+      return std::max<int64_t>(0, b - a);
+    };
+    const int64_t lo = bound(me), hi = bound(me + 1);
+    if (hi > lo) {
+      std::vector<uintptr_t> sl(static_cast<size_t>(n));
+      for (int m = 0; m < n; ++m)
+        sl[size_t(m)] = reinterpret_cast<uintptr_t>(remote_[size_t(m)].ptr) + uintptr_t(off + lo * es);
+      peer_scan(dev, s, op, dtype, exclusive, sl, sl, hi - lo);
+    }
+  }
+  drain("scan B2");
+  sync();  // B2: every prefix has landed at its owner and every read of my memory is finished
+  return true;
+}
+
 }  // namespace mpit

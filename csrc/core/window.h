@@ -109,6 +109,34 @@ class Window {
   bool allreduce_capable() const;
   static int64_t oneshot_bytes();  // MPIT_AR_ONESHOT_BYTES
 
+  // The window collectives (kernels.h peer_gather / peer_fold / peer_scan). Each is blocking and
+  // collective over the members, with allreduce's shape: stream synchronise, sync() (B1: inputs
+  // complete everywhere), at most one kernel launch on this rank, stream synchronise, sync() (B2:
+  // every read of my memory and every write into it has finished). Each returns false, before any
+  // synchronisation, when allreduce_capable() is false, and throws on a range error before B1.
+  // Local destinations are device memory for a device window and host memory for a host window.
+  //
+  // pull_gather: copy `bytes` bytes at byte offset `off` of member `member`'s window to `dst`,
+  // for up to 8 segments in one launch (all-gather(v), all-to-all, broadcast). A segment that
+  // names my own window at the address `dst` is dropped; an empty list takes part in the
+  // barriers only.
+  struct PullSeg {
+    int member;
+    int64_t off;
+    uintptr_t dst;
+    int64_t bytes;
+  };
+  bool pull_gather(const std::vector<PullSeg>& segs, hipStream_t s);
+  // pull_fold: dst[i] = fold over members [m0, m1) in member order of element i of the nelem
+  // elements at byte offset `off` of their windows (reduce-scatter: every rank its own segment;
+  // rooted reduce: the root alone). dst == 0 or nelem == 0: the barriers only.
+  bool pull_fold(int64_t off, int64_t nelem, int dtype, int op, uintptr_t dst, int m0, int m1, hipStream_t s);
+  // scan: in place at byte offset `off` of every member's window, member j ends with the fold of
+  // members 0..j (exclusive: 0..j-1, member 0's window untouched). Two-shot like allreduce: rank r
+  // loads slice r (the same 16-byte-rounded bounds) from all members and stores prefix j into
+  // member j, so every rank reads and writes the range once whatever the member count.
+  bool scan(int64_t off, int64_t nelem, int dtype, int op, bool exclusive, hipStream_t s);
+
  private:
   Engine& eng_;
   int64_t id_;
@@ -135,6 +163,7 @@ class Window {
   // the span check of a plan against member m's window; the strided base address, 0 for an empty plan
   uintptr_t plan_base(int m, int64_t off, const CopyPlan& p, const char* outside) const;
   void copy_plan(int dir, int m, int64_t off, const CopyPlan& p, uintptr_t packed, hipStream_t s);
+  int self_member() const;  // my index among the members (throws when I am none)
   void* ar_tmp_ = nullptr;  // one-shot in place: the private result, copied back after B2
   int64_t ar_tmp_bytes_ = 0;
 };

@@ -24,7 +24,7 @@
 
 #include "ew.h"
 #include "kernels.h"
-#include "peer_ops.h"  // the element tags, widen / narrow / comb (shared with type_acc.hip)
+#include "peer_ops.h"  // the element tags, widen / narrow / comb (shared with type_acc.hip), PeerTable, fold
 
 // plain IEEE operations in the stated order: no contraction anywhere in this file
 #pragma clang fp contract(off)
@@ -34,44 +34,6 @@ namespace {
 
 constexpr int kPB = 256;
 constexpr int kPGrid = 2048;
-
-struct PeerTable {
-  uint64_t src[kPeerMax];
-  uint64_t dst[kPeerMax];
-  int32_t ns, nd;
-};
-
-// x[0][e] = x[0][e] op x[1][e] op ... op x[ns-1][e]
-template <class Tag, int OP, int NS, int VE>
-MPIT_HD void fold(typename Tag::A (&x)[NS][VE], int ns) {
-#pragma unroll
-  for (int k = 1; k < NS; ++k) {
-    if (k < ns) {
-#pragma unroll
-      for (int e = 0; e < VE; ++e) x[0][e] = comb<Tag, OP>(x[0][e], x[k][e]);
-    }
-  }
-}
-
-template <class Tag, int NS, int VE>
-MPIT_HD void fold_op(int op, typename Tag::A (&x)[NS][VE], int ns) {
-  switch (op) {
-    case kPrSum: fold<Tag, kPrSum, NS, VE>(x, ns); break;
-    case kPrProd: fold<Tag, kPrProd, NS, VE>(x, ns); break;
-    case kPrMax: fold<Tag, kPrMax, NS, VE>(x, ns); break;
-    case kPrMin: fold<Tag, kPrMin, NS, VE>(x, ns); break;
-    case kPrLand: fold<Tag, kPrLand, NS, VE>(x, ns); break;
-    case kPrLor: fold<Tag, kPrLor, NS, VE>(x, ns); break;
-    case kPrLxor: fold<Tag, kPrLxor, NS, VE>(x, ns); break;
-    default:
-      if constexpr (Tag::kInt) {
-        if (op == kPrBand) fold<Tag, kPrBand, NS, VE>(x, ns);
-        else if (op == kPrBor) fold<Tag, kPrBor, NS, VE>(x, ns);
-        else fold<Tag, kPrBxor, NS, VE>(x, ns);
-      }
-      break;
-  }
-}
 
 // elements [0, head) and [head + nvec*VE, n) run scalar (head == n, nvec == 0: all of them)
 template <class Tag, int NS>

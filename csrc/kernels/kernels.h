@@ -396,6 +396,29 @@ int peer_dtype_size(int dtype);
 void peer_reduce(int dev, hipStream_t s, int op, int dtype, const std::vector<uintptr_t>& srcs,
                  const std::vector<uintptr_t>& dsts, int64_t n);
 
+// ---- the kernels of the window collectives (peer_coll.hip) -----------------------------
+// One launch on `s` each, or the host twin for dev < 0. Element types, ops, widening, rounding
+// and combine are peer_reduce's: the same operands give the same bits. No pointer of a call
+// needs to share its offset within 16 B with another (element alignment is all that is asked).
+// max_blocks: 0 = the production cap of the grid, > 0 = at most that many blocks (tests).
+// No cross-rank synchronisation inside; allocates and synchronises nothing.
+//
+// peer_gather: up to 8 independent byte segments, dst[g][0..bytes[g]) = src[g][0..bytes[g]), at
+// any alignment of either side. Zero-length segments and segments with src == dst are dropped;
+// destinations are disjoint from each other and from every source.
+void peer_gather(int dev, hipStream_t s, const std::vector<uintptr_t>& srcs, const std::vector<uintptr_t>& dsts,
+                 const std::vector<int64_t>& bytes, int max_blocks = 0);
+// peer_fold: dst[i] = src[0][i] (op) ... (op) src[ns-1][i], i < n, 1 <= ns <= 8, one destination
+// that aliases no source.
+void peer_fold(int dev, hipStream_t s, int op, int dtype, const std::vector<uintptr_t>& srcs, uintptr_t dst, int64_t n,
+               int max_blocks = 0);
+// peer_scan: inclusive dst[j][i] = src[0][i] (op) ... (op) src[j][i] for every j < ns; exclusive
+// dst[j][i] = src[0][i] (op) ... (op) src[j-1][i] for 1 <= j < ns, dst[0] never written (it may be
+// 0). The accumulator stays wide across the chain: a 16-bit float prefix is rounded once.
+// dst[j] may be src[j] (in place); nothing else may alias.
+void peer_scan(int dev, hipStream_t s, int op, int dtype, bool exclusive, const std::vector<uintptr_t>& srcs,
+               const std::vector<uintptr_t>& dsts, int64_t n, int max_blocks = 0);
+
 // ---- derived-datatype pack / unpack (type_copy.hip) ------------------------------------
 // dir 0: gather the strided layout at `strided` into the contiguous stream at `packed`; dir 1:
 // scatter the stream into the layout. The layout is up to three `loops` (count, byte stride),

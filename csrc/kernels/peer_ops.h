@@ -62,4 +62,43 @@ MPIT_HD typename Tag::A comb(typename Tag::A a, typename Tag::A b) {
   }
 }
 
+// the pointer table of the peer kernels (allreduce.hip, peer_coll.hip): by value in the kernel arguments
+struct PeerTable {
+  uint64_t src[kPeerMax];
+  uint64_t dst[kPeerMax];
+  int32_t ns, nd;
+};
+
+// x[0][e] = x[0][e] op x[1][e] op ... op x[ns-1][e]
+template <class Tag, int OP, int NS, int VE>
+MPIT_HD void fold(typename Tag::A (&x)[NS][VE], int ns) {
+#pragma unroll
+  for (int k = 1; k < NS; ++k) {
+    if (k < ns) {
+#pragma unroll
+      for (int e = 0; e < VE; ++e) x[0][e] = comb<Tag, OP>(x[0][e], x[k][e]);
+    }
+  }
+}
+
+template <class Tag, int NS, int VE>
+MPIT_HD void fold_op(int op, typename Tag::A (&x)[NS][VE], int ns) {
+  switch (op) {
+    case kPrSum: fold<Tag, kPrSum, NS, VE>(x, ns); break;
+    case kPrProd: fold<Tag, kPrProd, NS, VE>(x, ns); break;
+    case kPrMax: fold<Tag, kPrMax, NS, VE>(x, ns); break;
+    case kPrMin: fold<Tag, kPrMin, NS, VE>(x, ns); break;
+    case kPrLand: fold<Tag, kPrLand, NS, VE>(x, ns); break;
+    case kPrLor: fold<Tag, kPrLor, NS, VE>(x, ns); break;
+    case kPrLxor: fold<Tag, kPrLxor, NS, VE>(x, ns); break;
+    default:
+      if constexpr (Tag::kInt) {
+        if (op == kPrBand) fold<Tag, kPrBand, NS, VE>(x, ns);
+        else if (op == kPrBor) fold<Tag, kPrBor, NS, VE>(x, ns);
+        else fold<Tag, kPrBxor, NS, VE>(x, ns);
+      }
+      break;
+  }
+}
+
 }  // namespace mpit

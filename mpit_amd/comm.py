@@ -398,6 +398,10 @@ _PR_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2, torch.float
               torch.int64: 5, torch.uint8: 6}
 
 
+# the collectives with a window path (Comm.coll_stats keys)
+_WIN_COLLS = ("reduce_scatter", "allgather", "alltoall", "bcast", "reduce", "scan", "exscan")
+
+
 class _SymRec:
     """A registered symmetric range: [lo, hi) byte addresses of ``tensor``, exposed by ``win``."""
 
@@ -457,6 +461,7 @@ class Comm:
         self._ar_lock = threading.Lock()
         self._ar_calls = {"window": 0, "window_staged": 0, "p2p": 0, "rccl": 0}
         self._ar_off = False  # a member cannot run Window::allreduce: "window" falls back (agreed)
+        self._coll_calls = {c: {"window": 0, "window_staged": 0, "fallback": 0} for c in _WIN_COLLS}
 
     # ---------------------------------------------------------------- basics
     def Get_rank(self) -> int:
@@ -710,12 +715,19 @@ class Comm:
             rr.Wait()
             k <<= 1
 
-    def Bcast(self, buf: torch.Tensor, root: int = 0):
+    def Bcast(self, buf: torch.Tensor, root: int = 0, algo: Optional[str] = None):
+        """``algo``: see "window collectives" below (None: the MPIT_COLLECTIVES variable)."""
         n = self.Get_size()
         if n == 1:
             return buf
         t = _flat(buf)
-        if self._use_rccl(t):
+        algo = self._coll_algo(algo)
+        if algo == "window":
+            req = self._coll_bcast(t, root, keep=(buf,))
+            if req is not None:
+                req.Wait()
+                return buf
+        if algo != "p2p" and self._use_rccl(t):
             import torch.distributed as dist
 
             dist.broadcast(t, src=self._ranks[root], group=self._pg)
@@ -734,14 +746,21 @@ class Comm:
             mask >>= 1
         return buf
 
-    def Reduce(self, sendbuf, recvbuf, op: Op = SUM, root: int = 0):
+    def Reduce(self, sendbuf, recvbuf, op: Op = SUM, root: int = 0, algo: Optional[str] = None):
+        """``algo``: see "window collectives" below (None: the MPIT_COLLECTIVES variable)."""
         n = self.Get_size()
         src = _flat(sendbuf)
         if n == 1:
             if recvbuf is not None and recvbuf is not sendbuf:
                 _flat(recvbuf).copy_(src)
             return recvbuf
-        if self._use_rccl(src) and _rccl_op(op) is not None:
+        algo = self._coll_algo(algo)
+        if algo == "window":
+            req = self._coll_reduce(src, recvbuf, op, root, keep=(sendbuf, recvbuf))
+            if req is not None:
+                req.Wait()
+                return recvbuf
+        if algo != "p2p" and self._use_rccl(src) and _rccl_op(op) is not None:
             import torch.distributed as dist
 
             acc = src.clone()
@@ -820,10 +839,10 @@ class Comm:
             self._ring_allreduce(dst, op)
             return recvbuf
         tmp = torch.empty_like(src)
-        self.Reduce(src, tmp, op, 0)
+        self.Reduce(src, tmp, op, 0, algo="auto")
         if self.Get_rank() == 0:
             dst.copy_(tmp)
-        self.Bcast(dst, 0)
+        self.Bcast(dst, 0, algo="auto")
         return recvbuf
 
     def _ring_allreduce(self, buf: torch.Tensor, op: Op):
@@ -990,8 +1009,6 @@ class Comm:
         runs the blocking protocol there. Completion means complete for every stream.
         None (on every member alike): the window path is off for this communicator, the caller
         falls back to today's routing."""
-        import queue
-
         kind = "cuda" if src.is_cuda else "cpu"
         inplace = src.data_ptr() == dst.data_ptr()
         hit = self._sym_find(src)
@@ -1012,6 +1029,17 @@ class Comm:
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(src.device))
         req = Request(self, keep=keep, event=threading.Event())
+        self._ar_start()
+        self._ar_count("window")
+        if plan[0] == "staged":
+            self._ar_count("window_staged")
+        self._ar_q.put((plan, src, dst, _PR_OP_CODE[op], _PR_DTYPES[src.dtype], ev, req))
+        return req
+
+    def _ar_start(self):
+        """The FIFO worker of the window all-reduce and the window collectives (one per communicator)."""
+        import queue
+
         if self._ar_thread is None:
             self._ar_q = queue.Queue()
             if _rt.device() is not None:
@@ -1019,11 +1047,6 @@ class Comm:
             self._ar_thread = threading.Thread(target=self._ar_worker, args=(self._ar_q,), daemon=True,
                                                name=f"mpit-allreduce-{self._ctx}")
             self._ar_thread.start()
-        self._ar_count("window")
-        if plan[0] == "staged":
-            self._ar_count("window_staged")
-        self._ar_q.put((plan, src, dst, _PR_OP_CODE[op], _PR_DTYPES[src.dtype], ev, req))
-        return req
 
     def _ar_worker(self, q):
         if _rt.device() is not None:
@@ -1035,7 +1058,10 @@ class Comm:
                 return
             req = item[-1]
             try:
-                self._ar_exec(*item[:-1])
+                if item[0] == "coll":
+                    self._coll_exec(item[1], item[2])
+                else:
+                    self._ar_exec(*item[:-1])
             except BaseException as e:  # surfaced by Wait / Test
                 req._err = e
             req._ev.set()
@@ -1085,6 +1111,333 @@ class Comm:
             self._ar_thread.join()
             self._ar_thread = self._ar_q = None
 
+    # ---------------------------------------------------------------- window collectives
+    # Reduce_scatter(_block), Allgather(v), Alltoall, Bcast, Reduce, Scan, Exscan and the I* forms
+    # of the first five take ``algo``: ``auto`` (the routing without this section: RCCL when every
+    # rank owns its GPU, else the point-to-point algorithms), ``p2p`` (the point-to-point
+    # algorithms always) or ``window``; None reads the MPIT_COLLECTIVES variable (default
+    # ``auto``; MPIT_ALLREDUCE stays the all-reduce's alone). ``window``: one kernel launch
+    # (csrc/kernels/peer_coll.hip) between the two barriers of csrc/core/window.cpp
+    # Window::pull_gather / pull_fold / scan over symmetric memory, bitwise reproducible (member
+    # order is fold order). Every such call takes a ticket in the FIFO of the window all-reduce
+    # (:meth:`_ar_submit`): the same worker, the same stream, an event recorded on the caller's
+    # stream, so all-reduces and these collectives stay in call order on every rank and share the
+    # one staging window safely. Eligibility is the same on every rank: 2..8 members, a supported
+    # (op, dtype) for the folding ones, no member unable to map a window (``_ar_off``), tensors
+    # on this rank's device or on the host; what is not eligible takes ``auto`` on every member
+    # alike (counted as ``fallback`` in :meth:`coll_stats`).
+    # The contract is Allreduce's: the same call order, and the same registration state and
+    # in-place-ness of the buffers on every member (a buffer inside a symmetric range lies at the
+    # same offset of that range everywhere). A buffer inside a symmetric range (:meth:`sym_alloc`,
+    # :meth:`sym_register`) is read in place by the other members; anything else goes through the
+    # staging window (MPIT_AR_STAGE_MB) in pieces, and ``sendbuf`` is never modified. A rank whose
+    # part is empty still passes a (zero-length) view of its symmetric buffer, so that it takes
+    # the same plan as its peers.
+    def _coll_algo(self, algo: Optional[str]) -> str:
+        a = (algo if algo is not None else os.environ.get("MPIT_COLLECTIVES", "")) or "auto"
+        if a not in ("auto", "window", "p2p"):
+            raise ValueError(f"collective algo must be auto, window or p2p, not {a!r}")
+        return a
+
+    def coll_stats(self) -> dict:
+        """Calls with ``algo="window"`` per collective: ``window`` (of which ``window_staged`` went
+        through the staging buffer) and ``fallback`` (not eligible: today's routing)."""
+        with self._ar_lock:
+            return {k: dict(v) for k, v in self._coll_calls.items()}
+
+    def _coll_count(self, name: str, path: str):
+        with self._ar_lock:
+            self._coll_calls[name][path] += 1
+
+    @staticmethod
+    def _addr(t: torch.Tensor) -> int:
+        """The byte address of ``t``'s first element, of an empty view too (whose data_ptr() is 0)."""
+        return t.untyped_storage().data_ptr() + t.storage_offset() * t.element_size()
+
+    def _coll_sym(self, t: torch.Tensor, numel: Optional[int] = None):
+        """(native window, byte offset) of the symmetric range holding the first ``numel``
+        elements of ``t``, or None."""
+        p = self._addr(t)
+        nb = (t.numel() if numel is None else numel) * t.element_size()
+        for rec in self._sym:
+            if rec.lo <= p and p + nb <= rec.hi and rec.tensor.device == t.device:
+                return rec.win._w, p - rec.lo
+        return None
+
+    def _coll_ok(self, name: str, tensors, op: Optional[Op] = None) -> bool:
+        ok = 2 <= self.Get_size() <= 8 and self._rank != UNDEFINED and not self._ar_off
+        t0 = tensors[0]
+        for t in tensors:
+            ok = ok and t.dtype == t0.dtype and t.device == t0.device
+        ok = ok and (not t0.is_cuda or t0.device == _rt.device())
+        if ok and op is not None:
+            code, dt = _PR_OP_CODE.get(op), _PR_DTYPES.get(t0.dtype)
+            ok = code is not None and dt is not None and bool(native().peer_reduce_supported(code, dt))
+        if not ok:
+            self._coll_count(name, "fallback")
+        return ok
+
+    def _coll_overlap(self, a: torch.Tensor, na: int, b: torch.Tensor, nb: int) -> bool:
+        pa, pb = self._addr(a), self._addr(b)
+        return na > 0 and nb > 0 and pa < pb + nb * b.element_size() and pb < pa + na * a.element_size()
+
+    def _coll_stage(self, name: str, like: torch.Tensor):
+        """(native staging window, staging tensor), created collectively on the caller's thread;
+        None (on every member alike) when a member cannot map it."""
+        st = self._ar_staging("cuda" if like.is_cuda else "cpu")
+        if self._ar_off:
+            self._coll_count(name, "fallback")
+            return None
+        return self._sym_find(st)[0].win._w, st
+
+    def _coll_submit(self, name: str, staged: bool, fn, like: torch.Tensor, keep=()) -> Request:
+        """A ticket in the all-reduce FIFO for ``fn(stream pointer, torch stream or None)``."""
+        ev = None
+        if like.is_cuda:
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(like.device))
+        req = Request(self, keep=keep, event=threading.Event())
+        self._ar_start()
+        self._coll_count(name, "window")
+        if staged:
+            self._coll_count(name, "window_staged")
+        self._ar_q.put(("coll", fn, ev, req))
+        return req
+
+    def _coll_exec(self, fn, ev):
+        if ev is None:
+            fn(0, None)
+            return
+        s = self._ar_stream
+        with torch.cuda.stream(s):
+            ev.wait(s)  # what the caller queued before the call, and nothing later
+            fn(s.cuda_stream, s)
+            s.synchronize()
+
+    @staticmethod
+    def _coll_done(ok: bool):
+        if not ok:  # (not reachable: the capability is agreed on before any ticket is taken)
+            raise RuntimeError("mpit: this window cannot run the window collectives (member not mapped)")
+
+    def _coll_reduce_scatter(self, src, dst, counts, op, keep=()) -> Optional[Request]:
+        n, me = self.Get_size(), self.Get_rank()
+        if counts is None:
+            counts = [src.numel() // n] * n
+        if not self._coll_ok("reduce_scatter", (src, dst), op):
+            return None
+        counts = [int(c) for c in counts]
+        total, mine, d0 = sum(counts), counts[me], sum(counts[:me])
+        if src.numel() < total or dst.numel() < mine:
+            raise ValueError("Reduce_scatter: buffer shorter than its counts")
+        if self._coll_overlap(src, total, dst, mine):
+            raise ValueError("Reduce_scatter(algo='window'): recvbuf overlaps sendbuf")
+        es, code, dt = src.element_size(), _PR_OP_CODE[op], _PR_DTYPES[src.dtype]
+        out = self._addr(dst)
+        hit = self._coll_sym(src, total)
+        if hit is not None:
+            win, off = hit
+
+            def fn(sptr, stream):
+                self._coll_done(win.pull_fold(off + d0 * es, mine, dt, code, out if mine else 0, 0, n, sptr))
+        else:
+            plan = self._coll_stage("reduce_scatter", src)
+            if plan is None:
+                return None
+            win, st = plan
+            cap = st.numel() // es
+
+            def fn(sptr, stream):
+                for i in range(0, total, cap):
+                    m = min(cap, total - i)
+                    st[: m * es].view(src.dtype).copy_(src[i: i + m])
+                    lo, hi = max(i, d0), min(i + m, d0 + mine)
+                    if hi > lo:
+                        ok = win.pull_fold((lo - i) * es, hi - lo, dt, code, out + (lo - d0) * es, 0, n, sptr)
+                    else:
+                        ok = win.pull_fold(0, 0, dt, code, 0, 0, n, sptr)
+                    self._coll_done(ok)
+        return self._coll_submit("reduce_scatter", hit is None, fn, src, keep)
+
+    def _coll_reduce(self, src, recvbuf, op, root, keep=()) -> Optional[Request]:
+        n, me = self.Get_size(), self.Get_rank()
+        dst = _flat(recvbuf) if me == root else None
+        if not self._coll_ok("reduce", (src,) if dst is None else (src, dst), op):
+            return None
+        total = src.numel()
+        if dst is not None and dst.numel() < total:
+            raise ValueError("Reduce: recvbuf shorter than sendbuf")
+        if dst is not None and self._coll_overlap(src, total, dst, total):
+            raise ValueError("Reduce(algo='window'): recvbuf overlaps sendbuf")
+        es, code, dt = src.element_size(), _PR_OP_CODE[op], _PR_DTYPES[src.dtype]
+        out = self._addr(dst) if dst is not None else 0
+        hit = self._coll_sym(src)
+        if hit is not None:
+            win, off = hit
+
+            def fn(sptr, stream):
+                self._coll_done(win.pull_fold(off, total, dt, code, out, 0, n, sptr))
+        else:
+            plan = self._coll_stage("reduce", src)
+            if plan is None:
+                return None
+            win, st = plan
+            cap = st.numel() // es
+
+            def fn(sptr, stream):
+                for i in range(0, total, cap):
+                    m = min(cap, total - i)
+                    st[: m * es].view(src.dtype).copy_(src[i: i + m])
+                    self._coll_done(win.pull_fold(0, m, dt, code, out + i * es if out else 0, 0, n, sptr))
+        return self._coll_submit("reduce", hit is None, fn, src, keep)
+
+    def _coll_allgather(self, src, dst, counts, displs, keep=()) -> Optional[Request]:
+        n, me = self.Get_size(), self.Get_rank()
+        if not self._coll_ok("allgather", (src, dst)):
+            return None
+        if counts is None:
+            counts = [src.numel()] * n
+        counts = [int(c) for c in counts]
+        if displs is None:
+            displs = [sum(counts[:i]) for i in range(n)]
+        extent = max(d + c for d, c in zip(displs, counts))
+        if dst.numel() < extent or src.numel() < counts[me]:
+            raise ValueError("Allgatherv: buffer shorter than its counts")
+        es = src.element_size()
+        out = self._addr(dst)
+        hitd = self._coll_sym(dst, extent)
+        hit, staged = None, False
+        if hitd is not None and self._addr(src) == out + displs[me] * es:
+            # in place: my segment of the symmetric recvbuf is my contribution; pull the others'
+            win, off = hitd
+            segs = [(g, off + displs[g] * es, out + displs[g] * es, counts[g] * es) for g in range(n) if g != me]
+        else:
+            if self._coll_overlap(src, counts[me], dst, extent):
+                raise ValueError("Allgatherv(algo='window'): sendbuf overlaps recvbuf and is not this rank's segment")
+            hit = self._coll_sym(src, counts[me])
+            if hit is not None:
+                win, off = hit
+                segs = [(g, off, out + displs[g] * es, counts[g] * es) for g in range(n)]
+            else:
+                staged = True
+        if not staged:
+            def fn(sptr, stream):
+                self._coll_done(win.pull_gather(segs, sptr))
+        else:
+            plan = self._coll_stage("allgather", src)
+            if plan is None:
+                return None
+            win, st = plan
+            cap = st.numel() // es
+
+            def fn(sptr, stream):
+                for i in range(0, max(counts), cap):
+                    if counts[me] > i:
+                        m = min(cap, counts[me] - i)
+                        st[: m * es].view(src.dtype).copy_(src[i: i + m])
+                    sg = [(g, 0, out + (displs[g] + i) * es, min(cap, counts[g] - i) * es)
+                          for g in range(n) if counts[g] > i]
+                    self._coll_done(win.pull_gather(sg, sptr))
+        return self._coll_submit("allgather", staged, fn, src, keep)
+
+    def _coll_alltoall(self, src, dst, keep=()) -> Optional[Request]:
+        n, me = self.Get_size(), self.Get_rank()
+        if not self._coll_ok("alltoall", (src, dst)):
+            return None
+        c = src.numel() // n
+        if dst.numel() < c * n:
+            raise ValueError("Alltoall: recvbuf shorter than sendbuf")
+        if self._coll_overlap(src, c * n, dst, c * n):
+            raise ValueError("Alltoall(algo='window'): recvbuf overlaps sendbuf")
+        es = src.element_size()
+        out = self._addr(dst)
+        hit = self._coll_sym(src, c * n)
+        if hit is not None:
+            win, off = hit
+            segs = [(g, off + me * c * es, out + g * c * es, c * es) for g in range(n)]
+
+            def fn(sptr, stream):
+                self._coll_done(win.pull_gather(segs, sptr))
+        else:
+            plan = self._coll_stage("alltoall", src)
+            if plan is None:
+                return None
+            win, st = plan
+            cap = st.numel() // es
+
+            def fn(sptr, stream):
+                for i in range(0, c * n, cap):  # pieces of the flat send buffer; block `me` of each is mine
+                    m = min(cap, c * n - i)
+                    st[: m * es].view(src.dtype).copy_(src[i: i + m])
+                    lo, hi = max(i, me * c), min(i + m, (me + 1) * c)
+                    sg = [(g, (lo - i) * es, out + (g * c + lo - me * c) * es, (hi - lo) * es)
+                          for g in range(n)] if hi > lo else []
+                    self._coll_done(win.pull_gather(sg, sptr))
+        return self._coll_submit("alltoall", hit is None, fn, src, keep)
+
+    def _coll_bcast(self, t, root, keep=()) -> Optional[Request]:
+        me = self.Get_rank()
+        if not self._coll_ok("bcast", (t,)):
+            return None
+        es, total = t.element_size(), t.numel()
+        out = self._addr(t)
+        hit = self._coll_sym(t)
+        if hit is not None:
+            win, off = hit
+            segs = [(root, off, out, total * es)] if me != root else []
+
+            def fn(sptr, stream):
+                self._coll_done(win.pull_gather(segs, sptr))
+        else:
+            plan = self._coll_stage("bcast", t)
+            if plan is None:
+                return None
+            win, st = plan
+            cap = st.numel() // es
+
+            def fn(sptr, stream):
+                for i in range(0, total, cap):  # the root stages a piece, the others pull it into place
+                    m = min(cap, total - i)
+                    if me == root:
+                        st[: m * es].view(t.dtype).copy_(t[i: i + m])
+                    sg = [(root, 0, out + i * es, m * es)] if me != root else []
+                    self._coll_done(win.pull_gather(sg, sptr))
+        return self._coll_submit("bcast", hit is None, fn, t, keep)
+
+    def _coll_scan(self, src, dst, op, excl: bool, keep=()) -> Optional[Request]:
+        me = self.Get_rank()
+        name = "exscan" if excl else "scan"
+        if not self._coll_ok(name, (src, dst), op):
+            return None
+        total = src.numel()
+        if dst.numel() < total:
+            raise ValueError("Scan: recvbuf shorter than sendbuf")
+        inplace = self._addr(src) == self._addr(dst)
+        if not inplace and self._coll_overlap(src, total, dst, total):
+            raise ValueError("Scan(algo='window'): recvbuf overlaps sendbuf")
+        es, code, dt = src.element_size(), _PR_OP_CODE[op], _PR_DTYPES[src.dtype]
+        hit = self._coll_sym(src) if inplace else None
+        if hit is not None:
+            win, off = hit
+
+            def fn(sptr, stream):
+                self._coll_done(win.scan(off, total, dt, code, excl, sptr))
+        else:
+            plan = self._coll_stage(name, src)
+            if plan is None:
+                return None
+            win, st = plan
+            cap = st.numel() // es
+
+            def fn(sptr, stream):
+                for i in range(0, total, cap):
+                    m = min(cap, total - i)
+                    sv = st[: m * es].view(src.dtype)
+                    sv.copy_(src[i: i + m])
+                    self._coll_done(win.scan(0, m, dt, code, excl, sptr))
+                    if not (excl and me == 0):  # rank 0 of Exscan: recvbuf untouched, as MPI says
+                        dst[i: i + m].copy_(sv)
+        return self._coll_submit(name, hit is None, fn, src, keep)
+
     def _bg(self, fn, keep=()) -> Request:
         req = Request(self, keep=keep)
         with _coll_cv:
@@ -1111,20 +1464,54 @@ class Comm:
     def Ibarrier(self) -> Request:
         return self._bg(self.Barrier)
 
-    def Ibcast(self, buf, root=0) -> Request:
-        return self._bg(lambda: self.Bcast(buf, root), keep=(buf,))
+    # The non-blocking forms of the collectives with a window path: with ``algo="window"`` the
+    # ticket's Request (the FIFO of the window all-reduce, no thread per call); otherwise, and for
+    # what the window path cannot run, the blocking call on a background thread as before.
+    def Ibcast(self, buf, root=0, algo: Optional[str] = None) -> Request:
+        algo = self._coll_algo(algo)
+        if algo == "window" and self.Get_size() > 1:
+            req = self._coll_bcast(_flat(buf), root, keep=(buf,))
+            if req is not None:
+                return req
+        fb = "p2p" if algo == "p2p" else "auto"
+        return self._bg(lambda: self.Bcast(buf, root, algo=fb), keep=(buf,))
 
-    def Ireduce(self, sendbuf, recvbuf, op=SUM, root=0) -> Request:
-        return self._bg(lambda: self.Reduce(sendbuf, recvbuf, op, root), keep=(sendbuf, recvbuf))
+    def Ireduce(self, sendbuf, recvbuf, op=SUM, root=0, algo: Optional[str] = None) -> Request:
+        algo = self._coll_algo(algo)
+        if algo == "window" and self.Get_size() > 1:
+            req = self._coll_reduce(_flat(sendbuf), recvbuf, op, root, keep=(sendbuf, recvbuf))
+            if req is not None:
+                return req
+        fb = "p2p" if algo == "p2p" else "auto"
+        return self._bg(lambda: self.Reduce(sendbuf, recvbuf, op, root, algo=fb), keep=(sendbuf, recvbuf))
 
-    def Iallgather(self, sendbuf, recvbuf) -> Request:
-        return self._bg(lambda: self.Allgather(sendbuf, recvbuf), keep=(sendbuf, recvbuf))
+    def Iallgather(self, sendbuf, recvbuf, algo: Optional[str] = None) -> Request:
+        algo = self._coll_algo(algo)
+        if algo == "window":
+            req = self._coll_allgather(_flat(sendbuf), _flat(recvbuf), None, None, keep=(sendbuf, recvbuf))
+            if req is not None:
+                return req
+        fb = "p2p" if algo == "p2p" else "auto"
+        return self._bg(lambda: self.Allgather(sendbuf, recvbuf, algo=fb), keep=(sendbuf, recvbuf))
 
-    def Ialltoall(self, sendbuf, recvbuf) -> Request:
-        return self._bg(lambda: self.Alltoall(sendbuf, recvbuf), keep=(sendbuf, recvbuf))
+    def Ialltoall(self, sendbuf, recvbuf, algo: Optional[str] = None) -> Request:
+        algo = self._coll_algo(algo)
+        if algo == "window":
+            req = self._coll_alltoall(_flat(sendbuf), _flat(recvbuf), keep=(sendbuf, recvbuf))
+            if req is not None:
+                return req
+        fb = "p2p" if algo == "p2p" else "auto"
+        return self._bg(lambda: self.Alltoall(sendbuf, recvbuf, algo=fb), keep=(sendbuf, recvbuf))
 
-    def Ireduce_scatter(self, sendbuf, recvbuf, recvcounts=None, op=SUM) -> Request:
-        return self._bg(lambda: self.Reduce_scatter(sendbuf, recvbuf, recvcounts, op), keep=(sendbuf, recvbuf))
+    def Ireduce_scatter(self, sendbuf, recvbuf, recvcounts=None, op=SUM, algo: Optional[str] = None) -> Request:
+        algo = self._coll_algo(algo)
+        if algo == "window":
+            req = self._coll_reduce_scatter(_flat(sendbuf), _flat(recvbuf), recvcounts, op, keep=(sendbuf, recvbuf))
+            if req is not None:
+                return req
+        fb = "p2p" if algo == "p2p" else "auto"
+        return self._bg(lambda: self.Reduce_scatter(sendbuf, recvbuf, recvcounts, op, algo=fb),
+                        keep=(sendbuf, recvbuf))
 
     def Gatherv(self, sendbuf, recvbuf, counts: Optional[Sequence[int]] = None, displs=None, root: int = 0):
         n, me = self.Get_size(), self.Get_rank()
@@ -1174,11 +1561,19 @@ class Comm:
     def Scatter(self, sendbuf, recvbuf, root: int = 0):
         return self.Scatterv(sendbuf, recvbuf, None, None, root)
 
-    def Allgatherv(self, sendbuf, recvbuf, counts: Optional[Sequence[int]] = None, displs=None):
+    def Allgatherv(self, sendbuf, recvbuf, counts: Optional[Sequence[int]] = None, displs=None,
+                   algo: Optional[str] = None):
+        """``algo``: see "window collectives" above (None: the MPIT_COLLECTIVES variable)."""
         n = self.Get_size()
         src = _flat(sendbuf)
         dst = _flat(recvbuf)
-        if counts is None and self._use_rccl(src):
+        algo = self._coll_algo(algo)
+        if algo == "window":
+            req = self._coll_allgather(src, dst, counts, displs, keep=(sendbuf, recvbuf))
+            if req is not None:
+                req.Wait()
+                return recvbuf
+        if counts is None and algo != "p2p" and self._use_rccl(src):
             import torch.distributed as dist
 
             dist.all_gather_into_tensor(dst, src, group=self._pg)
@@ -1188,11 +1583,11 @@ class Comm:
         if displs is None:
             displs = [sum(counts[:i]) for i in range(n)]
         self.Gatherv(src, dst, counts, displs, 0)
-        self.Bcast(dst, 0)
+        self.Bcast(dst, 0, algo="auto")
         return recvbuf
 
-    def Allgather(self, sendbuf, recvbuf):
-        return self.Allgatherv(sendbuf, recvbuf, None, None)
+    def Allgather(self, sendbuf, recvbuf, algo: Optional[str] = None):
+        return self.Allgatherv(sendbuf, recvbuf, None, None, algo=algo)
 
     def Alltoallv(self, sendbuf, sendcounts, sdispls, recvbuf, recvcounts, rdispls):
         n, me = self.Get_size(), self.Get_rank()
@@ -1209,10 +1604,17 @@ class Comm:
         Request.Waitall(reqs)
         return recvbuf
 
-    def Alltoall(self, sendbuf, recvbuf):
+    def Alltoall(self, sendbuf, recvbuf, algo: Optional[str] = None):
+        """``algo``: see "window collectives" above (None: the MPIT_COLLECTIVES variable)."""
         n = self.Get_size()
         src, dst = _flat(sendbuf), _flat(recvbuf)
-        if self._use_rccl(src):
+        algo = self._coll_algo(algo)
+        if algo == "window":
+            req = self._coll_alltoall(src, dst, keep=(sendbuf, recvbuf))
+            if req is not None:
+                req.Wait()
+                return recvbuf
+        if algo != "p2p" and self._use_rccl(src):
             import torch.distributed as dist
 
             dist.all_to_all_single(dst, src, group=self._pg)
@@ -1234,30 +1636,44 @@ class Comm:
         Request.Waitall(reqs)
         return recvbufs
 
-    def Reduce_scatter(self, sendbuf, recvbuf, recvcounts: Optional[Sequence[int]] = None, op: Op = SUM):
+    def Reduce_scatter(self, sendbuf, recvbuf, recvcounts: Optional[Sequence[int]] = None, op: Op = SUM,
+                       algo: Optional[str] = None):
+        """``algo``: see "window collectives" above (None: the MPIT_COLLECTIVES variable)."""
         n = self.Get_size()
         src, dst = _flat(sendbuf), _flat(recvbuf)
         if recvcounts is None:
             recvcounts = [src.numel() // n] * n
-        if self._use_rccl(src) and _rccl_op(op) is not None and len(set(recvcounts)) == 1:
+        algo = self._coll_algo(algo)
+        if algo == "window":
+            req = self._coll_reduce_scatter(src, dst, recvcounts, op, keep=(sendbuf, recvbuf))
+            if req is not None:
+                req.Wait()
+                return recvbuf
+        if algo != "p2p" and self._use_rccl(src) and _rccl_op(op) is not None and len(set(recvcounts)) == 1:
             import torch.distributed as dist
 
             dist.reduce_scatter_tensor(dst[: recvcounts[0]], src[: recvcounts[0] * n].contiguous(),
                                        op=_rccl_op(op), group=self._pg)
             return recvbuf
         tmp = torch.empty_like(src) if self.Get_rank() == 0 else None
-        self.Reduce(src, tmp if tmp is not None else src, op, 0)
+        self.Reduce(src, tmp if tmp is not None else src, op, 0, algo="auto")
         displs = [sum(recvcounts[:i]) for i in range(n)]
         self.Scatterv(tmp, dst, recvcounts, displs, 0)
         return recvbuf
 
-    def Reduce_scatter_block(self, sendbuf, recvbuf, op: Op = SUM):
-        return self.Reduce_scatter(sendbuf, recvbuf, None, op)
+    def Reduce_scatter_block(self, sendbuf, recvbuf, op: Op = SUM, algo: Optional[str] = None):
+        return self.Reduce_scatter(sendbuf, recvbuf, None, op, algo=algo)
 
-    def Scan(self, sendbuf, recvbuf, op: Op = SUM):
-        """Inclusive prefix reduction (linear chain, order-preserving)."""
+    def Scan(self, sendbuf, recvbuf, op: Op = SUM, algo: Optional[str] = None):
+        """Inclusive prefix reduction (linear chain, order-preserving). ``algo``: see "window
+        collectives" above (None: the MPIT_COLLECTIVES variable)."""
         n, me = self.Get_size(), self.Get_rank()
         src, dst = _flat(sendbuf), _flat(recvbuf)
+        if self._coll_algo(algo) == "window":
+            req = self._coll_scan(src, dst, op, False, keep=(sendbuf, recvbuf))
+            if req is not None:
+                req.Wait()
+                return recvbuf
         acc = src.clone()
         if me > 0:
             prev = torch.empty_like(src)
@@ -1268,10 +1684,16 @@ class Comm:
         dst.copy_(acc)
         return recvbuf
 
-    def Exscan(self, sendbuf, recvbuf, op: Op = SUM):
-        """Exclusive prefix reduction; rank 0's recvbuf is left untouched (MPI)."""
+    def Exscan(self, sendbuf, recvbuf, op: Op = SUM, algo: Optional[str] = None):
+        """Exclusive prefix reduction; rank 0's recvbuf is left untouched (MPI). ``algo``: see
+        "window collectives" above (None: the MPIT_COLLECTIVES variable)."""
         n, me = self.Get_size(), self.Get_rank()
         src, dst = _flat(sendbuf), _flat(recvbuf)
+        if self._coll_algo(algo) == "window":
+            req = self._coll_scan(src, dst, op, True, keep=(sendbuf, recvbuf))
+            if req is not None:
+                req.Wait()
+                return recvbuf
         if me > 0:
             prev = torch.empty_like(src)
             self._crecv(prev, me - 1, 9).Wait()
@@ -1293,9 +1715,9 @@ class Comm:
         data = torch.frombuffer(bytearray(pickle.dumps(obj)), dtype=torch.uint8)
         n = torch.tensor([data.numel()], dtype=torch.int64)
         sizes = torch.zeros(self.Get_size(), dtype=torch.int64)
-        self.Allgather(n, sizes)
+        self.Allgather(n, sizes, algo="auto")
         buf = torch.zeros(int(sizes.sum()), dtype=torch.uint8)
-        self.Allgatherv(data, buf, sizes.tolist())
+        self.Allgatherv(data, buf, sizes.tolist(), algo="auto")
         out, o = [], 0
         for s in sizes.tolist():
             out.append(pickle.loads(buf[o: o + s].numpy().tobytes()))
