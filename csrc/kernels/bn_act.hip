@@ -1201,12 +1201,14 @@ __global__ __launch_bounds__(256) void bn_pool_fwd_kernel(const T* __restrict__ 
     Vec<float>::load(coef + g.C + c8 * 8, sh);
     float best[8];
     uint8_t arg[8];
+    const int h0 = ho * g.stride - g.pad, w0 = wo * g.stride - g.pad;
+    // as maxpool_fwd_kernel: the first in-range tap (t >= 0 always replaces it here)
+    const uint8_t first = uint8_t(max(0, -h0) * g.K + max(0, -w0));
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       best[e] = -__builtin_inff();
-      arg[e] = 0;
+      arg[e] = first;
     }
-    const int h0 = ho * g.stride - g.pad, w0 = wo * g.stride - g.pad;
     for (int i = 0; i < g.K; ++i) {
       const int h = h0 + i;
       if (unsigned(h) >= unsigned(g.H)) continue;

@@ -72,12 +72,15 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const T* __restrict__ 
     const int64_t n = int64_t(r / I(g.Ho));
     float best[8];
     uint8_t arg[8];
+    const int h0 = ho * g.stride - g.pad, w0 = wo * g.stride - g.pad;
+    // a window with nothing above -inf keeps its first in-range tap (tap 0 of a border window
+    // lies in the padding: no input pixel owns it)
+    const uint8_t first = uint8_t(max(0, -h0) * g.K + max(0, -w0));
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       best[e] = -__builtin_inff();
-      arg[e] = 0;
+      arg[e] = first;
     }
-    const int h0 = ho * g.stride - g.pad, w0 = wo * g.stride - g.pad;
     for (int i = 0; i < g.K; ++i) {
       const int h = h0 + i;
       if (unsigned(h) >= unsigned(g.H)) continue;
@@ -325,7 +328,9 @@ void maxpool_bwd_t(int dev, hipStream_t s, int N, int H, int W, int C, int K, in
                    uintptr_t idx, uintptr_t dx, uintptr_t ypool, uintptr_t db, uintptr_t ws) {
   const PoolGeo g = pool_geo(N, H, W, C, K, stride, pad);
   if ((dy | dx | ypool) % 16 || idx % 8) throw std::invalid_argument("maxpool_bwd: misaligned buffers");
-  if (db && (!ypool || !ws)) throw std::invalid_argument("maxpool_bwd: the bias gradient needs ypool and ws");
+  if (db && !ypool) throw std::invalid_argument("maxpool_bwd: the bias gradient needs ypool");
+  // (the fused-ReLU kernels write their per-block channel sums whether or not db is asked for)
+  if (ypool && !ws) throw std::invalid_argument("maxpool_bwd: the fused ReLU needs the workspace ws");
   if (ypool && 256 % (C / 8)) throw std::invalid_argument("maxpool_bwd: the fused ReLU needs 256 % (C / 8) == 0");
   hip_check(hipSetDevice(dev), "hipSetDevice");
   const auto* y = reinterpret_cast<const T*>(ypool);
