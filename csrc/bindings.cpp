@@ -670,6 +670,16 @@ PYBIND11_MODULE(_mpit, m) {
       py::arg("dev"), py::arg("stream"), py::arg("op"), py::arg("dtype"), py::arg("exclusive"), py::arg("srcs"),
       py::arg("dsts"), py::arg("n"), py::arg("max_blocks") = 0, py::call_guard<py::gil_scoped_release>());
   m.def("peer_reduce_supported", &peer_reduce_supported, py::arg("op"), py::arg("dtype"));
+  m.def("peer_dtype_size", &peer_dtype_size, py::arg("dtype"));
+  m.def("peer_dtype_align", &peer_dtype_align, py::arg("dtype"));
+  m.attr("PR_MAXLOC") = int(kPrMaxloc);
+  m.attr("PR_MINLOC") = int(kPrMinloc);
+  m.attr("PR_PAIR") = int(kPrPair);
+  m.attr("PR_FLOAT_INT") = int(kPrFloatInt);
+  m.attr("PR_DOUBLE_INT") = int(kPrDoubleInt);
+  m.attr("PR_LONG_INT") = int(kPrLongInt);
+  m.attr("ACC_REPLACE") = int(kAccReplace);
+  m.attr("ACC_NO_OP") = int(kAccNoOp);
   m.def(
       "peer_reduce",
       [](int dev, uintptr_t s, int op, int dtype, std::vector<uintptr_t> srcs, std::vector<uintptr_t> dsts, int64_t n) {

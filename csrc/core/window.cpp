@@ -380,9 +380,10 @@ bool Window::allreduce_capable() const {
 
 bool Window::allreduce(int64_t off, int64_t nelem, int dtype, int op, hipStream_t s, int mode, uintptr_t dst) {
   if (!allreduce_capable() || !peer_reduce_supported(op, dtype)) return false;
-  const int64_t es = peer_dtype_size(dtype);
+  const int64_t es = peer_dtype_size(dtype);  // a pair type: nelem counts pairs, es is the pair's extent
   const int n = int(remote_.size());
-  if (off < 0 || nelem < 0 || off % es) throw std::invalid_argument("mpit: window all-reduce range misaligned");
+  if (off < 0 || nelem < 0 || off % peer_dtype_align(dtype))
+    throw std::invalid_argument("mpit: window all-reduce range misaligned");
   for (const Remote& r : remote_)
     if (off + nelem * es > r.bytes) throw std::out_of_range("mpit: all-reduce range outside a member's window");
   const int dev = device_ ? eng_.device() : -1;
@@ -404,7 +405,7 @@ bool Window::allreduce(int64_t off, int64_t nelem, int dtype, int op, hipStream_
     // two-shot push: rank r reduces slice r from all members and stores it into all members.
     // Interior bounds rounded down to a 16-B address of member 0's range, from the alignment
     // member 0 published in its blob (checked against every mapping at connect), so every
-    // rank computes the same bounds.
+    // rank computes the same bounds. They count elements, so a slice never starts inside a pair.
     auto bound = [&](int k) -> int64_t {
       if (k <= 0) return 0;
       if (k >= n) return nelem;
@@ -493,9 +494,10 @@ bool Window::pull_fold(int64_t off, int64_t nelem, int dtype, int op, uintptr_t 
   if (!allreduce_capable() || !peer_reduce_supported(op, dtype)) return false;
   const int64_t es = peer_dtype_size(dtype);
   const int n = int(remote_.size());
-  if (off < 0 || nelem < 0 || off % es) throw std::invalid_argument("mpit: pull-fold range misaligned");
+  if (off < 0 || nelem < 0 || off % peer_dtype_align(dtype))
+    throw std::invalid_argument("mpit: pull-fold range misaligned");
   if (m0 < 0 || m1 > n || m0 >= m1) throw std::out_of_range("mpit: pull-fold member range");
-  if (dst % uintptr_t(es)) throw std::invalid_argument("mpit: pull-fold destination misaligned");
+  if (dst % uintptr_t(peer_dtype_align(dtype))) throw std::invalid_argument("mpit: pull-fold destination misaligned");
   const int dev = device_ ? eng_.device() : -1;
   self_member();
   std::vector<uintptr_t> srcs;
@@ -522,7 +524,8 @@ bool Window::scan(int64_t off, int64_t nelem, int dtype, int op, bool exclusive,
   if (!allreduce_capable() || !peer_reduce_supported(op, dtype)) return false;
   const int64_t es = peer_dtype_size(dtype);
   const int n = int(remote_.size());
-  if (off < 0 || nelem < 0 || off % es) throw std::invalid_argument("mpit: window scan range misaligned");
+  if (off < 0 || nelem < 0 || off % peer_dtype_align(dtype))
+    throw std::invalid_argument("mpit: window scan range misaligned");
   for (const Remote& r : remote_)
     if (off + nelem * es > r.bytes) throw std::out_of_range("mpit: scan range outside a member's window");
   const int dev = device_ ? eng_.device() : -1;

@@ -16,6 +16,13 @@
 // A scalar head and tail cover pointers that are not 16-B aligned (all of them must share
 // their offset within 16 B for the vector body; otherwise the whole range runs scalar) and
 // n that is no multiple of the vector width.
+// Pair types (MAXLOC / MINLOC, peer_ops.h): the element is a whole pair and its pointers are
+// aligned to the pair's largest member only (a float32 pair may sit at 4 mod 8), so a pair
+// boundary need not be a 16-B address and the pointers need not share their offset. Their body
+// is cut at dst[0] when a pair boundary of it is 16-B aligned and at element 0 otherwise, and
+// every access of it is a 16-byte one where it falls (gfx950 executes a global dwordx4 access at
+// any byte address; a second cache line per access at most). No pair is ever split between two
+// lanes or between head, body and tail; the scalar parts move whole pairs.
 // In place: every lane reads all the elements it owns before it writes any of them, and no
 // two lanes own the same element, so dst[j] may be src[j].
 // There is NO cross-rank communication in here: no flags, no spinning on peer memory.
@@ -55,7 +62,8 @@ __global__ __launch_bounds__(kPB) void peer_reduce_kernel(PeerTable tab, int op,
 #pragma unroll
         for (int k = 0; k < NS; ++k) {
           const S* p = reinterpret_cast<const S*>(tab.src[k < ns ? k : ns - 1]) + head;
-          raw[u][k] = reinterpret_cast<const uint4*>(p)[v];
+          if constexpr (Tag::kPair) __builtin_memcpy(&raw[u][k], reinterpret_cast<const uint8_t*>(p) + v * 16, 16);
+          else raw[u][k] = reinterpret_cast<const uint4*>(p)[v];
         }
       }
     }
@@ -77,7 +85,11 @@ __global__ __launch_bounds__(kPB) void peer_reduce_kernel(PeerTable tab, int op,
         for (int j = 0; j < VE; ++j) o[j] = narrow<Tag>(x[0][j]);
         uint4 out;
         __builtin_memcpy(&out, o, 16);
-        for (int j = 0; j < nd; ++j) reinterpret_cast<uint4*>(reinterpret_cast<S*>(tab.dst[j]) + head)[v] = out;
+        for (int j = 0; j < nd; ++j) {
+          S* q = reinterpret_cast<S*>(tab.dst[j]) + head;
+          if constexpr (Tag::kPair) __builtin_memcpy(reinterpret_cast<uint8_t*>(q) + v * 16, &out, 16);
+          else reinterpret_cast<uint4*>(q)[v] = out;
+        }
       }
     }
   }
@@ -132,7 +144,11 @@ void launch(int dev, hipStream_t s, int op, const std::vector<uintptr_t>& srcs, 
     vec = vec && (dsts[k] & 15) == mis;
   }
   int64_t head = n, nvec = 0;
-  if (vec) {
+  if constexpr (Tag::kPair) {  // accessed where it falls: nothing to share, and never a split pair
+    const uintptr_t dm = dsts[0] & 15;
+    head = dm % sizeof(S) == 0 ? std::min<int64_t>(n, int64_t((16 - dm) & 15) / int64_t(sizeof(S))) : 0;
+    nvec = (n - head) / VE;
+  } else if (vec) {
     head = std::min<int64_t>(n, int64_t((16 - mis) & 15) / int64_t(sizeof(S)));
     nvec = (n - head) / VE;
   }
@@ -156,19 +172,33 @@ void launch(int dev, hipStream_t s, int op, const std::vector<uintptr_t>& srcs, 
 }  // namespace
 
 bool peer_reduce_supported(int op, int dtype) {
+  if (peer_dtype_is_pair(dtype)) return op == kPrMaxloc || op == kPrMinloc;
   if (op < 0 || op >= kPrOps || dtype < 0 || dtype >= kPrDtypes) return false;
   const bool integer = dtype == kPrI32 || dtype == kPrI64 || dtype == kPrU8;
   return op < kPrBand || integer;
 }
 
-int peer_dtype_size(int dtype) {
+bool peer_dtype_is_pair(int dtype) {
+  return (dtype >= kPrPair && dtype < kPrPair + kPrDtypes) || (dtype >= kPrFloatInt && dtype <= kPrLongInt);
+}
+
+int peer_dtype_align(int dtype) {
   switch (dtype) {
-    case kPrF32: case kPrI32: return 4;
+    case kPrF32: case kPrI32: case kPrFloatInt: return 4;
     case kPrBf16: case kPrF16: return 2;
-    case kPrF64: case kPrI64: return 8;
+    case kPrF64: case kPrI64: case kPrDoubleInt: case kPrLongInt: return 8;
     case kPrU8: return 1;
-    default: throw std::invalid_argument("peer_reduce: unknown dtype");
+    default:
+      if (dtype >= kPrPair && dtype < kPrPair + kPrDtypes) return peer_dtype_align(dtype - kPrPair);
+      throw std::invalid_argument("peer_reduce: unknown dtype");
   }
+}
+
+int peer_dtype_size(int dtype) {
+  if (dtype >= kPrPair && dtype < kPrPair + kPrDtypes) return 2 * peer_dtype_align(dtype - kPrPair);
+  if (dtype == kPrFloatInt) return 8;
+  if (dtype == kPrDoubleInt || dtype == kPrLongInt) return 16;
+  return peer_dtype_align(dtype);
 }
 
 void peer_reduce(int dev, hipStream_t s, int op, int dtype, const std::vector<uintptr_t>& srcs,
@@ -176,21 +206,13 @@ void peer_reduce(int dev, hipStream_t s, int op, int dtype, const std::vector<ui
   if (!peer_reduce_supported(op, dtype)) throw std::invalid_argument("peer_reduce: unsupported (op, dtype)");
   if (srcs.empty() || srcs.size() > size_t(kPeerMax) || dsts.empty() || dsts.size() > size_t(kPeerMax))
     throw std::invalid_argument("peer_reduce: 1..8 sources and destinations");
-  const uintptr_t es = uintptr_t(peer_dtype_size(dtype));
+  const uintptr_t es = uintptr_t(peer_dtype_align(dtype));
   for (uintptr_t p : srcs)
     if (!p || p % es) throw std::invalid_argument("peer_reduce: null or misaligned source");
   for (uintptr_t p : dsts)
     if (!p || p % es) throw std::invalid_argument("peer_reduce: null or misaligned destination");
   if (n <= 0) return;
-  switch (dtype) {
-    case kPrF32: launch<TF32>(dev, s, op, srcs, dsts, n); break;
-    case kPrBf16: launch<TBf16>(dev, s, op, srcs, dsts, n); break;
-    case kPrF16: launch<TF16>(dev, s, op, srcs, dsts, n); break;
-    case kPrF64: launch<TF64>(dev, s, op, srcs, dsts, n); break;
-    case kPrI32: launch<TI32>(dev, s, op, srcs, dsts, n); break;
-    case kPrI64: launch<TI64>(dev, s, op, srcs, dsts, n); break;
-    default: launch<TU8>(dev, s, op, srcs, dsts, n); break;
-  }
+  with_peer_tag(dtype, [&](auto tag) { launch<decltype(tag)>(dev, s, op, srcs, dsts, n); });
 }
 
 }  // namespace mpit

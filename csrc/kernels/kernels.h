@@ -382,17 +382,34 @@ void bn_pool_bwd(int dev, hipStream_t s, bool bf16, int N, int H, int W, int C, 
 void avgpool_bwd(int dev, hipStream_t s, int N, int HW, int C, uintptr_t dy, uintptr_t dx, bool f32 = false);
 
 // ---- peer reduce: the reducer of the window all-reduce (allreduce.hip) ---------------
-enum PeerOp : int { kPrSum = 0, kPrProd, kPrMax, kPrMin, kPrLand, kPrLor, kPrLxor, kPrBand, kPrBor, kPrBxor, kPrOps };
-enum PeerDtype : int { kPrF32 = 0, kPrBf16, kPrF16, kPrF64, kPrI32, kPrI64, kPrU8, kPrDtypes };
+// kPrOps counts the ten element-wise ops. The two pair ops come after the AccOp codes (below), so
+// that every code handed out so far keeps its value.
+enum PeerOp : int {
+  kPrSum = 0, kPrProd, kPrMax, kPrMin, kPrLand, kPrLor, kPrLxor, kPrBand, kPrBor, kPrBxor, kPrOps,
+  kPrMaxloc = 12, kPrMinloc = 13
+};
+// kPrDtypes counts the seven scalar types. A pair layout of MAXLOC / MINLOC is one more element
+// type, and n then counts pairs: kPrPair + t is (value, index) interleaved in scalar type t
+// (2INT is kPrPair + kPrI32); the struct pairs are laid out as MPI lays them out:
+// FLOAT_INT f32 at 0, i32 at 4, extent 8; DOUBLE_INT f64 at 0, i32 at 8, extent 16; LONG_INT i64
+// at 0, i32 at 8, extent 16. Pointers of a pair type need the alignment of its largest member only.
+enum PeerDtype : int {
+  kPrF32 = 0, kPrBf16, kPrF16, kPrF64, kPrI32, kPrI64, kPrU8, kPrDtypes,
+  kPrPair = 16, kPrFloatInt = 24, kPrDoubleInt = 25, kPrLongInt = 26
+};
 constexpr int kPeerMax = 8;
 // dst[j][i] = src[0][i] (op) src[1][i] (op) ... (op) src[ns-1][i], i < n, for every j < nd:
 // a left fold in the order given; 1 <= ns <= 8, 1 <= nd <= 8; dev < 0 -> host twin.
 // bf16 / fp16 SUM and PROD accumulate in fp32 and round to nearest-even once at the store;
 // MAX / MIN propagate NaN; LAND / LOR / LXOR: non-zero is true, result 0 or 1 in the dtype;
-// BAND / BOR / BXOR: integer dtypes only. dst[j] may be src[j] (in place); nothing else may
+// BAND / BOR / BXOR: integer dtypes only. MAXLOC / MINLOC: the pair types only, and nothing else
+// on them; the result is one of the operand pairs, every byte of it (peer_ops.h has the rule).
+// dst[j] may be src[j] (in place); nothing else may
 // alias. The kernel holds no cross-rank synchronisation: visibility rests on its boundaries.
 bool peer_reduce_supported(int op, int dtype);
-int peer_dtype_size(int dtype);
+int peer_dtype_size(int dtype);   // bytes of one element: the extent of a pair
+int peer_dtype_align(int dtype);  // the alignment a pointer needs: that of the largest member
+bool peer_dtype_is_pair(int dtype);
 void peer_reduce(int dev, hipStream_t s, int op, int dtype, const std::vector<uintptr_t>& srcs,
                  const std::vector<uintptr_t>& dsts, int64_t n);
 
@@ -444,8 +461,9 @@ void type_copy(int dev, hipStream_t s, int dir, uintptr_t strided, uintptr_t pac
 // origin element) or kAccNoOp (store nothing: only meaningful with a fetch stream; packed may
 // be 0). dtype: a PeerDtype. `packed` and `fetch` are contiguous streams of the layout's packed
 // size. One item is `unit` bytes = unit / sizeof(element) elements: std::invalid_argument when
-// unit < sizeof(element), for an unsupported (op, dtype) (type_accumulate_supported: the ten of
-// peer_reduce_supported, REPLACE and NO_OP on all seven types) and for what type_copy refuses,
+// unit < sizeof(element) (a pair type's element is the whole pair), for an unsupported (op, dtype)
+// (type_accumulate_supported: what peer_reduce_supported takes, REPLACE and NO_OP on the seven
+// scalar types) and for what type_copy refuses,
 // before any launch. No atomics: the caller holds the target's exclusive lock. The layout is
 // trusted; overlapping target runs are erroneous (as for MPI_Accumulate) and undefined here.
 // Allocates and synchronises nothing.

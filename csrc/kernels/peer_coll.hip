@@ -14,7 +14,9 @@
 // peer_scan: the first one written) is 16-B aligned; every other pointer is accessed where it
 // falls, through a 16-byte __builtin_memcpy (gfx950 executes a global dwordx4 access at any byte
 // address; it costs a second cache line per access at most, never a scalar loop). Heads and
-// tails run scalar.
+// tails run scalar. A pair type (MAXLOC / MINLOC) is aligned to its largest member only, so its
+// destination may have no 16-B aligned pair boundary at all (a float32 pair at 4 mod 8): then the
+// body starts at element 0 and the destination too is stored where it falls. No pair is split.
 // peer_gather: blocks find their segment in a prefix table of per-segment tile counts, a
 // wave-uniform scan of at most 8 entries, so a long segment and a 3-byte one share the grid.
 // peer_scan: the accumulator stays wide across the chain (a 16-bit float prefix j is the fp32
@@ -160,7 +162,8 @@ __global__ __launch_bounds__(kCB) void peer_fold_kernel(PeerTable tab, int op, i
         for (int j = 0; j < VE; ++j) o[j] = narrow_acc<Tag>(x[0][j]);
         uint4 out;
         __builtin_memcpy(&out, o, 16);
-        *reinterpret_cast<uint4*>(dst + head + v * VE) = out;
+        if constexpr (Tag::kPair) store16(reinterpret_cast<uint8_t*>(dst + head + v * VE), out);  // where it falls
+        else *reinterpret_cast<uint4*>(dst + head + v * VE) = out;
       }
     }
   }
@@ -209,6 +212,11 @@ MPIT_HD void scan_chain(const typename Tag::S (&e)[NS][VE], int ns, bool excl, P
 
 template <class Tag, int NS, int VE, class Put>
 MPIT_HD void scan_op(int op, const typename Tag::S (&e)[NS][VE], int ns, bool excl, Put&& put) {
+  if constexpr (Tag::kPair) {
+    if (op == kPrMaxloc) scan_chain<Tag, kPrMaxloc, NS, VE>(e, ns, excl, put);
+    else scan_chain<Tag, kPrMinloc, NS, VE>(e, ns, excl, put);
+    return;
+  }
   switch (op) {
     case kPrSum: scan_chain<Tag, kPrSum, NS, VE>(e, ns, excl, put); break;
     case kPrProd: scan_chain<Tag, kPrProd, NS, VE>(e, ns, excl, put); break;
@@ -218,7 +226,7 @@ MPIT_HD void scan_op(int op, const typename Tag::S (&e)[NS][VE], int ns, bool ex
     case kPrLor: scan_chain<Tag, kPrLor, NS, VE>(e, ns, excl, put); break;
     case kPrLxor: scan_chain<Tag, kPrLxor, NS, VE>(e, ns, excl, put); break;
     default:
-      if constexpr (Tag::kInt) {
+      if constexpr (Tag::kInt && !Tag::kPair) {
         if (op == kPrBand) scan_chain<Tag, kPrBand, NS, VE>(e, ns, excl, put);
         else if (op == kPrBor) scan_chain<Tag, kPrBor, NS, VE>(e, ns, excl, put);
         else scan_chain<Tag, kPrBxor, NS, VE>(e, ns, excl, put);
@@ -304,10 +312,11 @@ void host_scan(int op, bool excl, const std::vector<uintptr_t>& srcs, const std:
 }
 
 // the cut of n elements at a destination: scalar head up to its next 16-B address, vectors, tail
+// (a pair type whose element boundaries never meet a 16-B address: no head)
 template <class S>
 void cut(uintptr_t dst, int64_t n, int64_t* head, int64_t* nvec) {
   constexpr int VE = 16 / int(sizeof(S));
-  *head = std::min<int64_t>(n, int64_t((16 - (dst & 15)) & 15) / int64_t(sizeof(S)));
+  *head = (dst & 15) % sizeof(S) ? 0 : std::min<int64_t>(n, int64_t((16 - (dst & 15)) & 15) / int64_t(sizeof(S)));
   *nvec = (n - *head) / VE;
 }
 
@@ -383,7 +392,7 @@ void check_fold_args(const char* who, int op, int dtype, const std::vector<uintp
   const std::string w(who);
   if (!peer_reduce_supported(op, dtype)) throw std::invalid_argument(w + ": unsupported (op, dtype)");
   if (srcs.empty() || srcs.size() > size_t(kPeerMax)) throw std::invalid_argument(w + ": 1..8 sources");
-  const uintptr_t es = uintptr_t(peer_dtype_size(dtype));
+  const uintptr_t es = uintptr_t(peer_dtype_align(dtype));
   for (uintptr_t p : srcs)
     if (!p || p % es) throw std::invalid_argument(w + ": null or misaligned source");
   for (uintptr_t p : dsts)
@@ -425,15 +434,7 @@ void peer_fold(int dev, hipStream_t s, int op, int dtype, const std::vector<uint
                int max_blocks) {
   check_fold_args("peer_fold", op, dtype, srcs, {dst});
   if (n <= 0) return;
-  switch (dtype) {
-    case kPrF32: launch_fold<TF32>(dev, s, op, srcs, dst, n, max_blocks); break;
-    case kPrBf16: launch_fold<TBf16>(dev, s, op, srcs, dst, n, max_blocks); break;
-    case kPrF16: launch_fold<TF16>(dev, s, op, srcs, dst, n, max_blocks); break;
-    case kPrF64: launch_fold<TF64>(dev, s, op, srcs, dst, n, max_blocks); break;
-    case kPrI32: launch_fold<TI32>(dev, s, op, srcs, dst, n, max_blocks); break;
-    case kPrI64: launch_fold<TI64>(dev, s, op, srcs, dst, n, max_blocks); break;
-    default: launch_fold<TU8>(dev, s, op, srcs, dst, n, max_blocks); break;
-  }
+  with_peer_tag(dtype, [&](auto tag) { launch_fold<decltype(tag)>(dev, s, op, srcs, dst, n, max_blocks); });
 }
 
 void peer_scan(int dev, hipStream_t s, int op, int dtype, bool exclusive, const std::vector<uintptr_t>& srcs,
@@ -443,15 +444,8 @@ void peer_scan(int dev, hipStream_t s, int op, int dtype, bool exclusive, const 
   check_fold_args("peer_scan", op, dtype, srcs,
                   exclusive && !dsts.empty() ? std::vector<uintptr_t>(dsts.begin() + 1, dsts.end()) : dsts);
   if (n <= 0) return;
-  switch (dtype) {
-    case kPrF32: launch_scan<TF32>(dev, s, op, exclusive, srcs, dsts, n, max_blocks); break;
-    case kPrBf16: launch_scan<TBf16>(dev, s, op, exclusive, srcs, dsts, n, max_blocks); break;
-    case kPrF16: launch_scan<TF16>(dev, s, op, exclusive, srcs, dsts, n, max_blocks); break;
-    case kPrF64: launch_scan<TF64>(dev, s, op, exclusive, srcs, dsts, n, max_blocks); break;
-    case kPrI32: launch_scan<TI32>(dev, s, op, exclusive, srcs, dsts, n, max_blocks); break;
-    case kPrI64: launch_scan<TI64>(dev, s, op, exclusive, srcs, dsts, n, max_blocks); break;
-    default: launch_scan<TU8>(dev, s, op, exclusive, srcs, dsts, n, max_blocks); break;
-  }
+  with_peer_tag(dtype,
+                [&](auto tag) { launch_scan<decltype(tag)>(dev, s, op, exclusive, srcs, dsts, n, max_blocks); });
 }
 
 }  // namespace mpit

@@ -2,7 +2,9 @@
 // all-reduce (allreduce.hip) and the one-sided accumulate (type_acc.hip) so that both give the
 // same bits for the same operands: bf16 / fp16 widen to fp32 and round once, integers wrap,
 // MAX / MIN propagate NaN, LAND / LOR / LXOR give 0 or 1 in the dtype, the bitwise ops are
-// integer-only (peer_reduce_supported). Host and device run the same functions.
+// integer-only (peer_reduce_supported). MAXLOC / MINLOC run on pair tags only: the element is a
+// whole (value, index) pair and the combine selects one operand, copied unchanged.
+// Host and device run the same functions.
 #pragma once
 #include <cstdint>
 #include <type_traits>
@@ -17,13 +19,39 @@
 namespace mpit {
 
 // element tags: S storage type, A accumulator type
-struct TF32 { using S = float; using A = float; static constexpr bool kInt = false; };
-struct TBf16 { using S = uint16_t; using A = float; static constexpr bool kInt = false; };
-struct TF16 { using S = uint16_t; using A = float; static constexpr bool kInt = false; };
-struct TF64 { using S = double; using A = double; static constexpr bool kInt = false; };
-struct TI32 { using S = int32_t; using A = int32_t; using U = uint32_t; static constexpr bool kInt = true; };
-struct TI64 { using S = int64_t; using A = int64_t; using U = uint64_t; static constexpr bool kInt = true; };
-struct TU8 { using S = uint8_t; using A = uint8_t; using U = uint8_t; static constexpr bool kInt = true; };
+struct TScalar { static constexpr bool kPair = false; };
+struct TF32 : TScalar { using S = float; using A = float; static constexpr bool kInt = false; };
+struct TBf16 : TScalar { using S = uint16_t; using A = float; static constexpr bool kInt = false; };
+struct TF16 : TScalar { using S = uint16_t; using A = float; static constexpr bool kInt = false; };
+struct TF64 : TScalar { using S = double; using A = double; static constexpr bool kInt = false; };
+struct TI32 : TScalar { using S = int32_t; using A = int32_t; using U = uint32_t; static constexpr bool kInt = true; };
+struct TI64 : TScalar { using S = int64_t; using A = int64_t; using U = uint64_t; static constexpr bool kInt = true; };
+struct TU8 : TScalar { using S = uint8_t; using A = uint8_t; using U = uint8_t; static constexpr bool kInt = true; };
+
+// A (value, index) pair of MAXLOC / MINLOC: value tag VT at byte 0, index tag IT at byte IOFF,
+// EXT bytes in all (padding included). The storage is the whole pair, aligned like its largest
+// member only: a float32 pair may sit at 4 mod 8. widen / narrow are the identity, so the pair
+// that wins keeps every byte: the sign of zero, a NaN's payload, padding, 16-bit values.
+template <class VT, class IT, int IOFF, int EXT>
+struct TPair {
+  using VTag = VT;
+  using ITag = IT;
+  static constexpr int kIdxOff = IOFF;
+  static constexpr int kAlign = int(sizeof(typename VT::S) > sizeof(typename IT::S) ? sizeof(typename VT::S)
+                                                                                    : sizeof(typename IT::S));
+  struct alignas(kAlign) S { uint8_t b[EXT]; };
+  using A = S;
+  static constexpr bool kInt = false;
+  static constexpr bool kPair = true;
+  static_assert(EXT == 2 || EXT == 4 || EXT == 8 || EXT == 16, "a pair divides a 16-byte vector");
+  static_assert(IOFF >= int(sizeof(typename VT::S)) && IOFF + int(sizeof(typename IT::S)) <= EXT && EXT % kAlign == 0,
+                "the members lie inside the pair");
+};
+template <class T>
+using THomPair = TPair<T, T, int(sizeof(typename T::S)), 2 * int(sizeof(typename T::S))>;  // interleaved, one dtype
+using TFloatInt = TPair<TF32, TI32, 4, 8>;    // MPI_FLOAT_INT
+using TDoubleInt = TPair<TF64, TI32, 8, 16>;  // MPI_DOUBLE_INT: 4 padding bytes
+using TLongInt = TPair<TI64, TI32, 8, 16>;    // MPI_LONG_INT: 4 padding bytes
 
 template <class Tag>
 MPIT_HD typename Tag::A widen(typename Tag::S v) {
@@ -38,10 +66,35 @@ MPIT_HD typename Tag::S narrow(typename Tag::A v) {
   else return v;
 }
 
+// true: MAXLOC / MINLOC (a, b) is b. The one definition of the rule (docs/ARCHITECTURE.md):
+// both values NaN: the smaller index, a on equal or NaN indices; one value NaN: that pair;
+// otherwise the better value, on equal values (-0 == +0) the smaller index, a on equal or NaN indices.
+template <class Tag, bool MAX>
+MPIT_HD bool loc_takes_b(const typename Tag::S& a, const typename Tag::S& b) {
+  using VT = typename Tag::VTag;
+  using IT = typename Tag::ITag;
+  typename VT::S sva, svb;
+  typename IT::S sia, sib;
+  __builtin_memcpy(&sva, a.b, sizeof(sva));
+  __builtin_memcpy(&svb, b.b, sizeof(svb));
+  __builtin_memcpy(&sia, a.b + Tag::kIdxOff, sizeof(sia));
+  __builtin_memcpy(&sib, b.b + Tag::kIdxOff, sizeof(sib));
+  const typename VT::A va = widen<VT>(sva), vb = widen<VT>(svb);  // 16-bit floats compare exactly in fp32
+  const typename IT::A ia = widen<IT>(sia), ib = widen<IT>(sib);
+  const bool an = va != va, bn = vb != vb;
+  if (an != bn) return bn;
+  if (!an) {
+    if (MAX ? vb > va : vb < va) return true;
+    if (MAX ? va > vb : va < vb) return false;
+  }
+  return ib < ia;  // false when either index is NaN
+}
+
 template <class Tag, int OP>
 MPIT_HD typename Tag::A comb(typename Tag::A a, typename Tag::A b) {
   using A = typename Tag::A;
-  if constexpr (OP == kPrLand) return A((a != A(0)) && (b != A(0)) ? 1 : 0);
+  if constexpr (Tag::kPair) return loc_takes_b<Tag, OP == kPrMaxloc>(a, b) ? b : a;
+  else if constexpr (OP == kPrLand) return A((a != A(0)) && (b != A(0)) ? 1 : 0);
   else if constexpr (OP == kPrLor) return A((a != A(0)) || (b != A(0)) ? 1 : 0);
   else if constexpr (OP == kPrLxor) return A((a != A(0)) != (b != A(0)) ? 1 : 0);
   else if constexpr (Tag::kInt) {
@@ -83,21 +136,50 @@ MPIT_HD void fold(typename Tag::A (&x)[NS][VE], int ns) {
 
 template <class Tag, int NS, int VE>
 MPIT_HD void fold_op(int op, typename Tag::A (&x)[NS][VE], int ns) {
-  switch (op) {
-    case kPrSum: fold<Tag, kPrSum, NS, VE>(x, ns); break;
-    case kPrProd: fold<Tag, kPrProd, NS, VE>(x, ns); break;
-    case kPrMax: fold<Tag, kPrMax, NS, VE>(x, ns); break;
-    case kPrMin: fold<Tag, kPrMin, NS, VE>(x, ns); break;
-    case kPrLand: fold<Tag, kPrLand, NS, VE>(x, ns); break;
-    case kPrLor: fold<Tag, kPrLor, NS, VE>(x, ns); break;
-    case kPrLxor: fold<Tag, kPrLxor, NS, VE>(x, ns); break;
-    default:
-      if constexpr (Tag::kInt) {
-        if (op == kPrBand) fold<Tag, kPrBand, NS, VE>(x, ns);
-        else if (op == kPrBor) fold<Tag, kPrBor, NS, VE>(x, ns);
-        else fold<Tag, kPrBxor, NS, VE>(x, ns);
-      }
-      break;
+  if constexpr (Tag::kPair) {  // the two pair ops and nothing else (peer_reduce_supported)
+    if (op == kPrMaxloc) fold<Tag, kPrMaxloc, NS, VE>(x, ns);
+    else fold<Tag, kPrMinloc, NS, VE>(x, ns);
+  } else {
+    switch (op) {
+      case kPrSum: fold<Tag, kPrSum, NS, VE>(x, ns); break;
+      case kPrProd: fold<Tag, kPrProd, NS, VE>(x, ns); break;
+      case kPrMax: fold<Tag, kPrMax, NS, VE>(x, ns); break;
+      case kPrMin: fold<Tag, kPrMin, NS, VE>(x, ns); break;
+      case kPrLand: fold<Tag, kPrLand, NS, VE>(x, ns); break;
+      case kPrLor: fold<Tag, kPrLor, NS, VE>(x, ns); break;
+      case kPrLxor: fold<Tag, kPrLxor, NS, VE>(x, ns); break;
+      default:
+        if constexpr (Tag::kInt) {
+          if (op == kPrBand) fold<Tag, kPrBand, NS, VE>(x, ns);
+          else if (op == kPrBor) fold<Tag, kPrBor, NS, VE>(x, ns);
+          else fold<Tag, kPrBxor, NS, VE>(x, ns);
+        }
+        break;
+    }
+  }
+}
+
+// one call per element type of a PeerDtype code the caller has checked (peer_reduce_supported)
+template <class F>
+void with_peer_tag(int dtype, F&& f) {
+  switch (dtype) {
+    case kPrF32: f(TF32{}); break;
+    case kPrBf16: f(TBf16{}); break;
+    case kPrF16: f(TF16{}); break;
+    case kPrF64: f(TF64{}); break;
+    case kPrI32: f(TI32{}); break;
+    case kPrI64: f(TI64{}); break;
+    case kPrU8: f(TU8{}); break;
+    case kPrPair + kPrF32: f(THomPair<TF32>{}); break;
+    case kPrPair + kPrBf16: f(THomPair<TBf16>{}); break;
+    case kPrPair + kPrF16: f(THomPair<TF16>{}); break;
+    case kPrPair + kPrF64: f(THomPair<TF64>{}); break;
+    case kPrPair + kPrI32: f(THomPair<TI32>{}); break;
+    case kPrPair + kPrI64: f(THomPair<TI64>{}); break;
+    case kPrPair + kPrU8: f(THomPair<TU8>{}); break;
+    case kPrFloatInt: f(TFloatInt{}); break;
+    case kPrDoubleInt: f(TDoubleInt{}); break;
+    default: f(TLongInt{}); break;
   }
 }
 

@@ -9,7 +9,9 @@
 // operands give the same bits in Accumulate and Allreduce.
 //
 // A lane loads its strided and its packed items for all kPerThread slots first, then combines,
-// then stores: 16 B per lane and stream when the layout allows. The op is wave-uniform and
+// then stores: 16 B per lane and stream when the layout allows. A pair type (MAXLOC / MINLOC) is
+// one more element type whose element is the whole pair: an item holds whole pairs, so the layout
+// must give unit >= the pair's size. The op is wave-uniform and
 // switched once per item. REPLACE stores the origin element and reads the target only for a
 // fetch; NO_OP stores nothing and never reads the origin (which may be absent).
 // There are NO atomics in here: mutual exclusion is the target window's exclusive lock
@@ -49,6 +51,11 @@ MPIT_HD void comb_all(const typename Tag::S (&t)[VE], const typename Tag::S (&o)
 template <class Tag, int VE>
 MPIT_HD void comb_op(int op, const typename Tag::S (&t)[VE], const typename Tag::S (&o)[VE],
                      typename Tag::S (&r)[VE]) {
+  if constexpr (Tag::kPair) {
+    if (op == kPrMaxloc) comb_all<Tag, kPrMaxloc, VE>(t, o, r);
+    else comb_all<Tag, kPrMinloc, VE>(t, o, r);
+    return;
+  }
   switch (op) {
     case kPrSum: comb_all<Tag, kPrSum, VE>(t, o, r); break;
     case kPrProd: comb_all<Tag, kPrProd, VE>(t, o, r); break;
@@ -58,7 +65,7 @@ MPIT_HD void comb_op(int op, const typename Tag::S (&t)[VE], const typename Tag:
     case kPrLor: comb_all<Tag, kPrLor, VE>(t, o, r); break;
     case kPrLxor: comb_all<Tag, kPrLxor, VE>(t, o, r); break;
     default:
-      if constexpr (Tag::kInt) {
+      if constexpr (Tag::kInt && !Tag::kPair) {
         if (op == kPrBand) comb_all<Tag, kPrBand, VE>(t, o, r);
         else if (op == kPrBor) comb_all<Tag, kPrBor, VE>(t, o, r);
         else comb_all<Tag, kPrBxor, VE>(t, o, r);
@@ -150,7 +157,7 @@ void host_acc(const TaArgs& a, const tl::Checked& c, const int64_t* offs, const 
           S* sp = reinterpret_cast<S*>(base + (offs ? offs[r] : 0));
           const int64_t ne = len / int64_t(sizeof(S));
           for (int64_t e = 0; e < ne; ++e) {
-            S t[1] = {sp[e]}, o[1] = {op != kAccNoOp ? pp[e] : S(0)}, res[1] = {t[0]};
+            S t[1] = {sp[e]}, o[1] = {op != kAccNoOp ? pp[e] : S{}}, res[1] = {t[0]};
             if (op == kAccReplace) sp[e] = o[0];
             else if (op != kAccNoOp) {
               comb_op<Tag, 1>(op, t, o, res);
@@ -187,6 +194,7 @@ void bad(const std::string& what) { throw std::invalid_argument("mpit: type_accu
 }  // namespace
 
 bool type_accumulate_supported(int op, int dtype) {
+  if (peer_dtype_is_pair(dtype)) return peer_reduce_supported(op, dtype);  // the two pair ops and nothing else
   if (dtype < 0 || dtype >= kPrDtypes) return false;
   return op == kAccReplace || op == kAccNoOp || peer_reduce_supported(op, dtype);
 }
@@ -199,7 +207,10 @@ void type_accumulate(int dev, hipStream_t s, int op, int dtype, uintptr_t stride
   if (!strided) bad("null target");
   if (!packed && op != kAccNoOp) bad("an origin stream is needed unless the op is NO_OP");
   const tl::Checked c = tl::check_layout("type_accumulate", strided, packed, loops, table, R, L, per, unit);
-  if (unit < es) bad("unit is smaller than the element");
+  if (unit < es)
+    bad(peer_dtype_is_pair(dtype) ? "unit " + std::to_string(unit) + " is smaller than the pair of " +
+                                        std::to_string(es) + " bytes"
+                                  : std::string("unit is smaller than the element"));
   if (fetch % uintptr_t(unit)) bad("unit does not divide the layout");
   if (c.bytes == 0) return;
   if (op == kAccNoOp && !fetch) return;  // nothing to store anywhere
@@ -212,15 +223,7 @@ void type_accumulate(int dev, hipStream_t s, int op, int dtype, uintptr_t stride
   const int mode = tl::layout_mode(table, R, L);
   wide = wide || c.bytes >= (int64_t(1) << 32);
   const dim3 grid = tl::layout_grid(a.lay.items, max_blocks);
-  switch (dtype) {
-    case kPrF32: run<TF32>(dev, s, a, c, unit, mode, grid, wide); break;
-    case kPrBf16: run<TBf16>(dev, s, a, c, unit, mode, grid, wide); break;
-    case kPrF16: run<TF16>(dev, s, a, c, unit, mode, grid, wide); break;
-    case kPrF64: run<TF64>(dev, s, a, c, unit, mode, grid, wide); break;
-    case kPrI32: run<TI32>(dev, s, a, c, unit, mode, grid, wide); break;
-    case kPrI64: run<TI64>(dev, s, a, c, unit, mode, grid, wide); break;
-    default: run<TU8>(dev, s, a, c, unit, mode, grid, wide); break;
-  }
+  with_peer_tag(dtype, [&](auto tag) { run<decltype(tag)>(dev, s, a, c, unit, mode, grid, wide); });
 }
 
 }  // namespace mpit

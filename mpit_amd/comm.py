@@ -17,6 +17,8 @@ Transport is chosen by the tensor's device inside one native core (SURVEY §7.4 
 """
 from __future__ import annotations
 
+import functools
+import inspect
 import os
 import threading
 from typing import Callable, List, Optional, Sequence
@@ -352,12 +354,50 @@ class Op:
         return f"Op({self.name})"
 
 
-def _loc(better):
+class _PairLayout:
+    """How a buffer of MAXLOC / MINLOC pairs is laid out: the value dtype at byte 0, the index
+    dtype at byte ``ioff``, ``ext`` bytes per pair (padding included), pointers aligned to
+    ``align`` (the largest member). ``code`` is the kernels' element type (kernels.h PeerDtype);
+    ``carrier`` a torch dtype of exactly ``ext`` bytes: a buffer viewed in it counts pairs, so
+    every count, displacement and staging cut made on the view falls on a pair boundary."""
+
+    __slots__ = ("name", "vdt", "idt", "ioff", "ext", "align", "code", "carrier")
+
+    def __init__(self, name, vdt, idt, ioff, ext, align, code):
+        self.name, self.vdt, self.idt, self.ioff, self.ext = name, vdt, idt, ioff, ext
+        self.align, self.code = align, code
+        self.carrier = {2: torch.int16, 4: torch.int32, 8: torch.int64, 16: torch.complex128}[ext]
+
+    def members(self, t: torch.Tensor):
+        """(pairs as [k, ext] bytes, values [k], indices [k]) of a contiguous buffer of whole pairs."""
+        raw = t.reshape(-1).view(torch.uint8).view(-1, self.ext)
+        vs = self.vdt.itemsize
+        if self.vdt == self.idt and self.ioff == vs:  # interleaved, one dtype: strided views, no copy
+            both = raw.view(self.vdt)
+            return raw, both[:, 0], both[:, 1]
+        v = raw[:, :vs].contiguous().view(self.vdt).reshape(-1)
+        i = raw[:, self.ioff: self.ioff + self.idt.itemsize].contiguous().view(self.idt).reshape(-1)
+        return raw, v, i
+
+
+def _loc(maximum: bool, lay: Optional[_PairLayout] = None):
+    """MAXLOC / MINLOC on flat buffers of k pairs, the rule of csrc/kernels/peer_ops.h
+    loc_takes_b bit for bit: exactly one value NaN: that pair; otherwise the better value; on
+    equal values (or both NaN) the smaller index, and a on equal or NaN indices. The result is one
+    of the operand pairs, every byte of it. ``lay`` None: interleaved pairs of the tensors' dtype."""
     def f(a, b):
-        # (value, index) pairs in the last dimension; ties keep the smaller index
-        va, ia, vb, ib = a[..., 0], a[..., 1], b[..., 0], b[..., 1]
-        take_b = better(vb, va) | ((vb == va) & (ib < ia))
-        return torch.stack([torch.where(take_b, vb, va), torch.where(take_b, ib, ia)], dim=-1)
+        ly = lay if lay is not None else _hom_layout(a.dtype)
+        if a.numel() * a.element_size() % ly.ext or a.numel() * a.element_size() != b.numel() * b.element_size():
+            raise ValueError(f"{'MAXLOC' if maximum else 'MINLOC'}: the operands hold whole {ly.name} pairs, "
+                             "as many in each")
+        ra, va, ia = ly.members(a.contiguous())
+        rb, vb, ib = ly.members(b.contiguous())
+        an, bn = va != va, vb != vb
+        both = ~an & ~bn
+        b_wins = both & ((vb > va) if maximum else (vb < va))
+        a_wins = both & ((va > vb) if maximum else (va < vb))
+        take_b = torch.where(an != bn, bn, b_wins | (~a_wins & (ib < ia)))
+        return torch.where(take_b[:, None], rb, ra).reshape(-1).view(a.dtype).view(a.shape)
 
     return f
 
@@ -374,8 +414,8 @@ LXOR = Op(lambda a, b: (a.bool() ^ b.bool()).to(a.dtype), name="LXOR")
 BAND = Op(lambda a, b: a & b, name="BAND")
 BOR = Op(lambda a, b: a | b, name="BOR")
 BXOR = Op(lambda a, b: a ^ b, name="BXOR")
-MAXLOC = Op(_loc(lambda x, y: x > y), name="MAXLOC")
-MINLOC = Op(_loc(lambda x, y: x < y), name="MINLOC")
+MAXLOC = Op(_loc(True), name="MAXLOC")
+MINLOC = Op(_loc(False), name="MINLOC")
 REPLACE = Op(lambda a, b: b, commute=False, name="REPLACE")
 NO_OP = Op(lambda a, b: a, commute=False, name="NO_OP")
 OP_NULL = None
@@ -386,16 +426,179 @@ def Op_create(fn: Callable, commute: bool = True) -> Op:
     return Op(fn, commute)
 
 
-def Reduce_local(inbuf: torch.Tensor, inoutbuf: torch.Tensor, op: Op = SUM):
-    """MPI_Reduce_local (skipped by the reference's generator, readspec.py:73-75)."""
-    inoutbuf.copy_(op(inbuf, inoutbuf))
+def Reduce_local(inbuf: torch.Tensor, inoutbuf: torch.Tensor, op: Op = SUM, pairtype=None):
+    """MPI_Reduce_local (skipped by the reference's generator, readspec.py:73-75). ``pairtype``:
+    the pair datatype of a MAXLOC / MINLOC buffer (None: interleaved pairs of the tensor's dtype)."""
+    op, (a, b), _, bounced = _pair_bind("Reduce_local", op, pairtype, (inbuf, inoutbuf))
+    b.copy_(op(a, b))
+    _pair_unbounce(bounced, (inoutbuf,))
     return inoutbuf
 
 
-# (op, dtype) codes of the peer-reduce kernel (csrc/kernels/kernels.h PeerOp / PeerDtype)
-_PR_OP_CODE = {SUM: 0, PROD: 1, MAX: 2, MIN: 3, LAND: 4, LOR: 5, LXOR: 6, BAND: 7, BOR: 8, BXOR: 9}
+# (op, dtype) codes of the peer-reduce kernel (csrc/kernels/kernels.h PeerOp / PeerDtype). The two
+# pair ops come after REPLACE / NO_OP (10, 11: window.py), and run on the pair element types only.
+_PR_OP_CODE = {SUM: 0, PROD: 1, MAX: 2, MIN: 3, LAND: 4, LOR: 5, LXOR: 6, BAND: 7, BOR: 8, BXOR: 9,
+               MAXLOC: 12, MINLOC: 13}
 _PR_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2, torch.float64: 3, torch.int32: 4,
               torch.int64: 5, torch.uint8: 6}
+_PR_PAIR = 16  # kPrPair + a _PR_DTYPES code: interleaved pairs of that dtype
+_PAIR_STRUCTS = {  # datatypes._pair layouts the kernels have: name -> (value, index offset, extent, align, code)
+    "MPI_FLOAT_INT": (torch.float32, 4, 8, 4, 24),
+    "MPI_DOUBLE_INT": (torch.float64, 8, 16, 8, 25),
+    "MPI_LONG_INT": (torch.int64, 8, 16, 8, 26),
+}
+_pair_layouts = {}
+
+
+def _hom_layout(dtype: torch.dtype) -> _PairLayout:
+    ly = _pair_layouts.get(dtype)
+    if ly is None:
+        code = _PR_DTYPES.get(dtype)
+        if code is None:
+            raise TypeError(f"MAXLOC / MINLOC: no pairs of {dtype} elements (one of {list(_PR_DTYPES)})")
+        es = dtype.itemsize
+        ly = _pair_layouts[dtype] = _PairLayout(f"{dtype} x 2", dtype, dtype, es, 2 * es, es, _PR_PAIR + code)
+    return ly
+
+
+def _pair_layout(pairtype, dtype: torch.dtype) -> _PairLayout:
+    """The layout ``pairtype`` names (None: interleaved pairs of ``dtype``). TypeError, naming the
+    type, for a datatype that is no pair type or whose layout the kernels do not have."""
+    if pairtype is None:
+        return _hom_layout(dtype)
+    name = getattr(pairtype, "_name", None) or repr(pairtype)
+    if name == "MPI_2INT":
+        return _hom_layout(torch.int32)
+    ly = _pair_layouts.get(name)
+    if ly is None:
+        spec = _PAIR_STRUCTS.get(name)
+        tm = getattr(pairtype, "typemap", None)
+        if spec is None or tm is None or len(tm) != 2 or tm[1][0] != spec[1] or pairtype.extent != spec[2]:
+            raise TypeError(f"MAXLOC / MINLOC: {name} is not a supported pair datatype "
+                            "(FLOAT_INT, DOUBLE_INT, LONG_INT, 2INT, or None for pairs of the tensor's dtype)")
+        ly = _pair_layouts[name] = _PairLayout(name, spec[0], torch.int32, spec[1], spec[2], spec[3], spec[4])
+    return ly
+
+
+class _PairOp(Op):
+    """MAXLOC / MINLOC bound to a pair layout, on carrier views (one element = one pair). Not
+    marked commutative: a NaN float index compares with nothing, so only the left fold in rank
+    order is defined, and the point-to-point paths then give the window kernels' bytes."""
+
+    def __init__(self, base: Op, lay: _PairLayout):
+        super().__init__(_loc(base is MAXLOC, lay), commute=False, name=base.name)
+        self.base, self.lay = base, lay
+
+
+_pair_ops = {}
+
+
+def _pair_bind(what: str, op: Op, pairtype, bufs, counts=None):
+    """The public reducing calls start here. Any other op: ``pairtype`` must be None, nothing
+    changes. MAXLOC / MINLOC: (the op bound to its layout, the buffers as flat carrier views that
+    count pairs, ``counts`` in pairs, the bounced buffers). Raises before any communication:
+    ValueError for a buffer that holds no whole number of pairs, odd ``counts`` of interleaved
+    elements or an address not aligned to the pair's largest member, TypeError for a pair type
+    without kernels. A buffer aligned to the member but not to the pair (a float32 view from an odd
+    element) has no carrier view: it is bounced through an aligned copy, ``(copy, flat buffer)`` in
+    the last result, which the caller writes back where the buffer is an output
+    (:func:`_pair_unbounce`)."""
+    if isinstance(op, _PairOp):
+        return op, bufs, counts, ()  # an inner call: bound already
+    if op is not MAXLOC and op is not MINLOC:
+        if pairtype is not None:
+            raise ValueError(f"{what}: pairtype goes with MAXLOC / MINLOC only, not with {op!r}")
+        return op, bufs, counts, ()
+    first = next(b for b in bufs if b is not None)
+    lay = _pair_layout(pairtype, first.dtype)
+    out, bounced = [], []
+    for b in bufs:
+        if b is None:
+            out.append(None)
+            continue
+        again = next((o for o, p in zip(out, bufs) if p is b), None)
+        if again is not None:  # in place: one view for both
+            out.append(again)
+            continue
+        t = _flat(b)
+        if pairtype is None and t.dtype != lay.vdt:
+            raise ValueError(f"{what}: {op.name} buffers of {t.dtype} and {lay.vdt} elements")
+        nb = _nbytes(t)
+        if nb % lay.ext:
+            raise ValueError(f"{what}: {op.name} needs whole {lay.name} pairs of {lay.ext} bytes, the buffer has "
+                             f"{t.numel()} elements ({nb} bytes)")
+        addr = t.untyped_storage().data_ptr() + t.storage_offset() * t.element_size()
+        if addr % lay.align:
+            raise ValueError(f"{what}: a buffer of {lay.name} pairs must be aligned to {lay.align} bytes")
+        if addr % lay.ext:
+            tmp = torch.empty(nb // lay.ext, dtype=lay.carrier, device=t.device)
+            tmp.view(torch.uint8).copy_(t.view(torch.uint8))
+            bounced.append((tmp, t))
+            out.append(tmp)
+        else:
+            out.append(t.view(torch.uint8).view(lay.carrier))
+    if counts is not None and pairtype is None:
+        if any(int(c) % 2 for c in counts):
+            raise ValueError(f"{what}: {op.name} counts of interleaved elements must be even")
+        counts = [int(c) // 2 for c in counts]
+    key = (op, lay.name)
+    bound = _pair_ops.get(key)
+    if bound is None:
+        bound = _pair_ops[key] = _PairOp(op, lay)
+    return bound, out, counts, bounced
+
+
+def _pair_unbounce(bounced, outputs):
+    """Write the aligned copies of :func:`_pair_bind` back into the caller's output buffers."""
+    for tmp, t in bounced:
+        if any(o is not None and o.data_ptr() == t.data_ptr() for o in outputs):
+            t.view(torch.uint8).copy_(tmp.view(torch.uint8))
+
+
+def _pair_call(fn):
+    """A reducing method of Comm that takes ``pairtype``: with MAXLOC / MINLOC it runs on the
+    carrier views of :func:`_pair_bind` and the op bound to the layout (``recvcounts`` in pairs),
+    and hands the caller's own buffer back; with any other op it runs as it is."""
+    names = list(inspect.signature(fn).parameters)
+    i_op, i_pt = names.index("op") - 1, names.index("pairtype") - 1
+    sig = inspect.signature(fn)
+
+    @functools.wraps(fn)
+    def call(self, *args, **kw):
+        op = args[i_op] if len(args) > i_op else kw.get("op", SUM)
+        if op is not MAXLOC and op is not MINLOC:
+            if (args[i_pt] if len(args) > i_pt else kw.get("pairtype")) is not None and not isinstance(op, _PairOp):
+                raise ValueError(f"{fn.__name__}: pairtype goes with MAXLOC / MINLOC only, not with {op!r}")
+            return fn(self, *args, **kw)
+        ba = sig.bind(self, *args, **kw)
+        a = ba.arguments
+        send, recv = a["sendbuf"], a.get("recvbuf")
+        bound, (s2, r2), counts, bounced = _pair_bind(fn.__name__, op, a.get("pairtype"), (send, recv),
+                                                      a.get("recvcounts"))
+        a["op"], a["sendbuf"], a["pairtype"] = bound, s2, None
+        if "recvbuf" in a:
+            a["recvbuf"] = r2
+        if "recvcounts" in a:
+            a["recvcounts"] = counts
+        out = fn(*ba.args, **ba.kwargs)
+        outputs = (recv,) if recv is not None or "root" in a else (send,)  # (recvbuf None: in place, but for Reduce)
+        if isinstance(out, Request):
+            out._keep = (getattr(out, "_keep", None), send, recv)
+            if bounced:  # (a bounced buffer completes the call here: its copy goes back before the caller looks)
+                out.Wait()
+                _pair_unbounce(bounced, outputs)
+            return out
+        _pair_unbounce(bounced, outputs)
+        return recv if recv is not None and (out is r2 or out is s2) else (send if out is s2 else out)
+
+    return call
+
+
+def _pr_codes(op: Op, dtype: torch.dtype):
+    """(op code, element type code) for the kernels, None where there is none."""
+    if isinstance(op, _PairOp):
+        return _PR_OP_CODE[op.base], op.lay.code
+    return _PR_OP_CODE.get(op), _PR_DTYPES.get(dtype)
 
 
 # the collectives with a window path (Comm.coll_stats keys)
@@ -746,7 +949,8 @@ class Comm:
             mask >>= 1
         return buf
 
-    def Reduce(self, sendbuf, recvbuf, op: Op = SUM, root: int = 0, algo: Optional[str] = None):
+    @_pair_call
+    def Reduce(self, sendbuf, recvbuf, op: Op = SUM, root: int = 0, algo: Optional[str] = None, pairtype=None):
         """``algo``: see "window collectives" below (None: the MPIT_COLLECTIVES variable)."""
         n = self.Get_size()
         src = _flat(sendbuf)
@@ -803,7 +1007,8 @@ class Comm:
             _flat(recvbuf).copy_(acc)
         return recvbuf
 
-    def Allreduce(self, sendbuf, recvbuf=None, op: Op = SUM, algo: Optional[str] = None):
+    @_pair_call
+    def Allreduce(self, sendbuf, recvbuf=None, op: Op = SUM, algo: Optional[str] = None, pairtype=None):
         """MPI_Allreduce (mpifuncs.c:83). ``sendbuf is recvbuf`` (IN_PLACE) allowed.
         ``algo``: None (the MPIT_ALLREDUCE variable, default ``auto``) | ``auto`` (RCCL when
         every rank owns its GPU, else the point-to-point ring / tree) | ``p2p`` (the ring /
@@ -875,7 +1080,8 @@ class Comm:
             rq.Wait()
             sq.Wait()
 
-    def Iallreduce(self, sendbuf, recvbuf=None, op: Op = SUM, algo: Optional[str] = None) -> Request:
+    @_pair_call
+    def Iallreduce(self, sendbuf, recvbuf=None, op: Op = SUM, algo: Optional[str] = None, pairtype=None) -> Request:
         """Non-blocking all-reduce (mpifuncs.c:1357). RCCL work handle on HBM tensors,
         a background progress thread otherwise; ``algo="window"``: a ticket in the
         communicator's all-reduce FIFO (:meth:`Allreduce`, :meth:`_ar_submit`)."""
@@ -986,7 +1192,7 @@ class Comm:
             rec.win.Free()
 
     def _win_ok(self, src: torch.Tensor, dst: torch.Tensor, op: Op) -> bool:
-        code, dt = _PR_OP_CODE.get(op), _PR_DTYPES.get(src.dtype)
+        code, dt = _pr_codes(op, src.dtype)
         if code is None or dt is None or self.Get_size() > 8 or self._rank == UNDEFINED or self._ar_off:
             return False
         if dst.dtype != src.dtype or dst.device != src.device or dst.numel() != src.numel():
@@ -1033,7 +1239,7 @@ class Comm:
         self._ar_count("window")
         if plan[0] == "staged":
             self._ar_count("window_staged")
-        self._ar_q.put((plan, src, dst, _PR_OP_CODE[op], _PR_DTYPES[src.dtype], ev, req))
+        self._ar_q.put((plan, src, dst) + _pr_codes(op, src.dtype) + (ev, req))
         return req
 
     def _ar_start(self):
@@ -1171,7 +1377,7 @@ class Comm:
             ok = ok and t.dtype == t0.dtype and t.device == t0.device
         ok = ok and (not t0.is_cuda or t0.device == _rt.device())
         if ok and op is not None:
-            code, dt = _PR_OP_CODE.get(op), _PR_DTYPES.get(t0.dtype)
+            code, dt = _pr_codes(op, t0.dtype)
             ok = code is not None and dt is not None and bool(native().peer_reduce_supported(code, dt))
         if not ok:
             self._coll_count(name, "fallback")
@@ -1231,7 +1437,7 @@ class Comm:
             raise ValueError("Reduce_scatter: buffer shorter than its counts")
         if self._coll_overlap(src, total, dst, mine):
             raise ValueError("Reduce_scatter(algo='window'): recvbuf overlaps sendbuf")
-        es, code, dt = src.element_size(), _PR_OP_CODE[op], _PR_DTYPES[src.dtype]
+        es, (code, dt) = src.element_size(), _pr_codes(op, src.dtype)
         out = self._addr(dst)
         hit = self._coll_sym(src, total)
         if hit is not None:
@@ -1268,7 +1474,7 @@ class Comm:
             raise ValueError("Reduce: recvbuf shorter than sendbuf")
         if dst is not None and self._coll_overlap(src, total, dst, total):
             raise ValueError("Reduce(algo='window'): recvbuf overlaps sendbuf")
-        es, code, dt = src.element_size(), _PR_OP_CODE[op], _PR_DTYPES[src.dtype]
+        es, (code, dt) = src.element_size(), _pr_codes(op, src.dtype)
         out = self._addr(dst) if dst is not None else 0
         hit = self._coll_sym(src)
         if hit is not None:
@@ -1414,7 +1620,7 @@ class Comm:
         inplace = self._addr(src) == self._addr(dst)
         if not inplace and self._coll_overlap(src, total, dst, total):
             raise ValueError("Scan(algo='window'): recvbuf overlaps sendbuf")
-        es, code, dt = src.element_size(), _PR_OP_CODE[op], _PR_DTYPES[src.dtype]
+        es, (code, dt) = src.element_size(), _pr_codes(op, src.dtype)
         hit = self._coll_sym(src) if inplace else None
         if hit is not None:
             win, off = hit
@@ -1476,7 +1682,8 @@ class Comm:
         fb = "p2p" if algo == "p2p" else "auto"
         return self._bg(lambda: self.Bcast(buf, root, algo=fb), keep=(buf,))
 
-    def Ireduce(self, sendbuf, recvbuf, op=SUM, root=0, algo: Optional[str] = None) -> Request:
+    @_pair_call
+    def Ireduce(self, sendbuf, recvbuf, op=SUM, root=0, algo: Optional[str] = None, pairtype=None) -> Request:
         algo = self._coll_algo(algo)
         if algo == "window" and self.Get_size() > 1:
             req = self._coll_reduce(_flat(sendbuf), recvbuf, op, root, keep=(sendbuf, recvbuf))
@@ -1503,7 +1710,9 @@ class Comm:
         fb = "p2p" if algo == "p2p" else "auto"
         return self._bg(lambda: self.Alltoall(sendbuf, recvbuf, algo=fb), keep=(sendbuf, recvbuf))
 
-    def Ireduce_scatter(self, sendbuf, recvbuf, recvcounts=None, op=SUM, algo: Optional[str] = None) -> Request:
+    @_pair_call
+    def Ireduce_scatter(self, sendbuf, recvbuf, recvcounts=None, op=SUM, algo: Optional[str] = None,
+                        pairtype=None) -> Request:
         algo = self._coll_algo(algo)
         if algo == "window":
             req = self._coll_reduce_scatter(_flat(sendbuf), _flat(recvbuf), recvcounts, op, keep=(sendbuf, recvbuf))
@@ -1636,8 +1845,9 @@ class Comm:
         Request.Waitall(reqs)
         return recvbufs
 
+    @_pair_call
     def Reduce_scatter(self, sendbuf, recvbuf, recvcounts: Optional[Sequence[int]] = None, op: Op = SUM,
-                       algo: Optional[str] = None):
+                       algo: Optional[str] = None, pairtype=None):
         """``algo``: see "window collectives" above (None: the MPIT_COLLECTIVES variable)."""
         n = self.Get_size()
         src, dst = _flat(sendbuf), _flat(recvbuf)
@@ -1661,10 +1871,12 @@ class Comm:
         self.Scatterv(tmp, dst, recvcounts, displs, 0)
         return recvbuf
 
-    def Reduce_scatter_block(self, sendbuf, recvbuf, op: Op = SUM, algo: Optional[str] = None):
+    @_pair_call
+    def Reduce_scatter_block(self, sendbuf, recvbuf, op: Op = SUM, algo: Optional[str] = None, pairtype=None):
         return self.Reduce_scatter(sendbuf, recvbuf, None, op, algo=algo)
 
-    def Scan(self, sendbuf, recvbuf, op: Op = SUM, algo: Optional[str] = None):
+    @_pair_call
+    def Scan(self, sendbuf, recvbuf, op: Op = SUM, algo: Optional[str] = None, pairtype=None):
         """Inclusive prefix reduction (linear chain, order-preserving). ``algo``: see "window
         collectives" above (None: the MPIT_COLLECTIVES variable)."""
         n, me = self.Get_size(), self.Get_rank()
@@ -1684,7 +1896,8 @@ class Comm:
         dst.copy_(acc)
         return recvbuf
 
-    def Exscan(self, sendbuf, recvbuf, op: Op = SUM, algo: Optional[str] = None):
+    @_pair_call
+    def Exscan(self, sendbuf, recvbuf, op: Op = SUM, algo: Optional[str] = None, pairtype=None):
         """Exclusive prefix reduction; rank 0's recvbuf is left untouched (MPI). ``algo``: see
         "window collectives" above (None: the MPIT_COLLECTIVES variable)."""
         n, me = self.Get_size(), self.Get_rank()

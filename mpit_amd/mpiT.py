@@ -273,21 +273,37 @@ def Bcast(buf, count, datatype, root, comm):
     return SUCCESS
 
 
+def _is_pair_type(datatype) -> bool:
+    return any(datatype is t for t in (FLOAT_INT, DOUBLE_INT, LONG_INT, SHORT_INT, TWOINT, LONG_DOUBLE_INT))
+
+
+def _loc_args(op, datatype, count, *bufs):
+    """The buffers of a reducing wrapper cut to ``count``, and the keywords that go with them.
+    MAXLOC / MINLOC with one of the pair datatypes: ``count`` counts pairs of that type, which
+    passes through as ``pairtype`` (TypeError from there for SHORT_INT / LONG_DOUBLE_INT). Anything
+    else is as it was: ``count`` elements of the tensors, the datatype unused."""
+    if (op is MAXLOC or op is MINLOC) and _is_pair_type(datatype):
+        nb = int(count) * datatype.extent
+        return [None if b is None else b.reshape(-1)[: nb // b.element_size()] for b in bufs], {"pairtype": datatype}
+    return [None if b is None else b.reshape(-1)[:count] for b in bufs], {}
+
+
 def Reduce(sendbuf, recvbuf, count, datatype, op, root, comm):
-    comm.Reduce(sendbuf.reshape(-1)[:count], recvbuf.reshape(-1)[:count] if recvbuf is not None else None, op, root)
+    (s, r), kw = _loc_args(op, datatype, count, sendbuf, recvbuf)
+    comm.Reduce(s, r, op, root, **kw)
     return SUCCESS
 
 
 def Allreduce(sendbuf, recvbuf, count, datatype, op, comm):
     """mpifuncs.c:83 — ``sendbuf is recvbuf`` works as MPI_IN_PLACE."""
-    s = sendbuf.reshape(-1)[:count]
-    r = recvbuf.reshape(-1)[:count]
-    comm.Allreduce(s, r, op)
+    (s, r), kw = _loc_args(op, datatype, count, sendbuf, recvbuf)
+    comm.Allreduce(s, r, op, **kw)
     return SUCCESS
 
 
 def Iallreduce(sendbuf, recvbuf, count, datatype, op, comm):
-    return comm.Iallreduce(sendbuf.reshape(-1)[:count], recvbuf.reshape(-1)[:count], op)
+    (s, r), kw = _loc_args(op, datatype, count, sendbuf, recvbuf)
+    return comm.Iallreduce(s, r, op, **kw)
 
 
 def Gather(sendbuf, sendcount, sendtype, recvbuf, recvcount, recvtype, root, comm):
@@ -336,17 +352,22 @@ def Alltoallw(sendbufs, recvbufs, comm):
 
 
 def Reduce_scatter(sendbuf, recvbuf, recvcounts, datatype, op, comm):
-    comm.Reduce_scatter(sendbuf, recvbuf, recvcounts, op)
+    if (op is MAXLOC or op is MINLOC) and _is_pair_type(datatype):  # recvcounts count pairs
+        comm.Reduce_scatter(sendbuf, recvbuf, recvcounts, op, pairtype=datatype)
+    else:
+        comm.Reduce_scatter(sendbuf, recvbuf, recvcounts, op)
     return SUCCESS
 
 
 def Scan(sendbuf, recvbuf, count, datatype, op, comm):
-    comm.Scan(sendbuf.reshape(-1)[:count], recvbuf.reshape(-1)[:count], op)
+    (s, r), kw = _loc_args(op, datatype, count, sendbuf, recvbuf)
+    comm.Scan(s, r, op, **kw)
     return SUCCESS
 
 
 def Exscan(sendbuf, recvbuf, count, datatype, op, comm):
-    comm.Exscan(sendbuf.reshape(-1)[:count], recvbuf.reshape(-1)[:count], op)
+    (s, r), kw = _loc_args(op, datatype, count, sendbuf, recvbuf)
+    comm.Exscan(s, r, op, **kw)
     return SUCCESS
 
 
@@ -573,6 +594,21 @@ def _acc_kernel(what, data, result, edt, target_rank, target_disp, target_count,
     return True
 
 
+def _loc_acc(what, origin, count, pairtype, result, target_rank, target_disp, target_count, target_type, op, win):
+    """MAXLOC / MINLOC of the one-sided wrappers: ``count`` pairs of ``pairtype``, onto as many
+    contiguous pairs of the same type at the target (Win.Accumulate / Win.Get_accumulate)."""
+    if target_type is not pairtype or int(target_count) != int(count):
+        raise ValueError(f"{what}: {op.name} needs the origin's pair datatype and count at the target")
+    if origin is None:
+        raise ValueError(f"{what}: only NO_OP goes without an origin buffer")
+    (o, r), kw = _loc_args(op, pairtype, count, origin, result)
+    if result is None:
+        win.Accumulate(o, target_rank, target_disp, op, **kw)
+    else:
+        win.Get_accumulate(o, r, target_rank, target_disp, op, **kw)
+    return SUCCESS
+
+
 def Accumulate(origin, origin_count, origin_type, target_rank, target_disp, target_count, target_type, op, win):
     """MPI_Accumulate (mpifuncs.c:9): target = op(target, origin) element by element over the
     target datatype's layout; both type maps must hold one element type. Every predefined
@@ -582,6 +618,9 @@ def Accumulate(origin, origin_count, origin_type, target_rank, target_disp, targ
     REPLACE of fp32 / bf16, one axpby launch per contiguous run of the target datatype."""
     from .comm import REPLACE, SUM
 
+    if (op is MAXLOC or op is MINLOC) and _is_pair_type(origin_type):
+        return _loc_acc("Accumulate", origin, origin_count, origin_type, None, target_rank, target_disp, target_count,
+                        target_type, op, win)
     data, edt = _origin_stream(origin, origin_count, origin_type)
     op = op or SUM
     if _acc_kernel("Accumulate", data, None, edt, target_rank, target_disp, target_count, target_type, op, win) is True:
@@ -613,6 +652,11 @@ def Get_accumulate(origin, origin_count, origin_type, result, result_count, resu
     path does not serve the call this raises with the reason."""
     from .comm import NO_OP, SUM
 
+    if (op is MAXLOC or op is MINLOC) and _is_pair_type(result_type):
+        if origin_type is not result_type or int(origin_count) != int(result_count):
+            raise ValueError("Get_accumulate: MAXLOC / MINLOC take the same pairs as origin and result")
+        return _loc_acc("Get_accumulate", origin, origin_count, origin_type, result, target_rank, target_disp,
+                        target_count, target_type, op, win)
     op = op or SUM
     if origin is None:
         if op is not NO_OP:

@@ -46,7 +46,7 @@ def host_view(ptr: int, nbytes: int, dtype: torch.dtype) -> torch.Tensor:
     return torch.frombuffer(buf, dtype=dtype)
 
 
-ACC_REPLACE, ACC_NO_OP = 10, 11  # csrc/kernels/kernels.h AccOp, after the ten PeerOp codes
+ACC_REPLACE, ACC_NO_OP = 10, 11  # csrc/kernels/kernels.h AccOp, after the ten element-wise PeerOp codes
 
 _contig_plans = {}
 
@@ -73,10 +73,12 @@ def acc_codes(what: str, op, dtype):
     """(op, dtype) codes of type_accumulate, or None when the kernel is off or `op` is not one of
     its twelve (the caller falls back or refuses). TypeError, naming both, for one of its ops on
     an element type it does not have: a float bitwise op, a type outside the seven."""
-    from .comm import _PR_DTYPES, _PR_OP_CODE, NO_OP, REPLACE
+    from .comm import _PR_DTYPES, _PR_OP_CODE, NO_OP, REPLACE, _PairOp
 
     if not _dt.kernel_enabled():
         return None
+    if isinstance(op, _PairOp):  # MAXLOC / MINLOC bound to its pair layout (comm._pair_bind)
+        return _PR_OP_CODE[op.base], op.lay.code
     code = _PR_OP_CODE.get(op)
     if code is None:
         code = ACC_REPLACE if op is REPLACE else (ACC_NO_OP if op is NO_OP else None)
@@ -168,14 +170,39 @@ class Win:
         self._w.get(origin.data_ptr(), target_rank, target_disp * self.disp_unit,
                     origin.numel() * origin.element_size(), self._stream())
 
-    def Accumulate(self, origin: torch.Tensor, target_rank: int, target_disp: int = 0, op=None):
+    def _pair_acc(self, what: str, op, pairtype, origin, result, target_rank: int, target_disp: int):
+        """MAXLOC / MINLOC of Accumulate / Get_accumulate: whole pairs of ``pairtype`` (None:
+        interleaved pairs of the tensor's dtype), one type_accumulate launch whose element is the
+        pair. ValueError, naming both, when the addresses give an item smaller than the pair."""
+        from .comm import _pair_bind, _pair_unbounce
+
+        bound, (o, r), _, bounced = _pair_bind(what, op, pairtype, (origin.contiguous(), result))
+        codes = acc_codes(what, bound, o.dtype)
+        if codes is None:
+            raise ValueError(f"{what}: {acc_unavailable(op)}")
+        ext = bound.lay.ext
+        if r is not None and r.numel() != o.numel():
+            raise ValueError(f"{what}: origin and result hold the same pairs")
+        if not self._plan_acc(o, r, target_rank, target_disp * self.disp_unit, contiguous_plan(o.numel() * ext), codes,
+                              ext):
+            raise ValueError(f"{what}: {op.name} moves whole pairs of {ext} bytes; the origin, result and target "
+                             "addresses give a smaller unit")
+        _pair_unbounce(bounced, (result,))
+        _dt.COUNTERS["rma_acc_kernel"] += 1
+
+    def Accumulate(self, origin: torch.Tensor, target_rank: int, target_disp: int = 0, op=None, pairtype=None):
         """target = op(target, origin) element by element: every predefined reduction, REPLACE and
         NO_OP on fp32 / bf16 / fp16 / fp64 / int32 / int64 / uint8 in one type_accumulate launch
-        (with MPIT_DTYPE_KERNEL=0: SUM / REPLACE on fp32 / bf16 through the axpby kernel). Atomic
+        (with MPIT_DTYPE_KERNEL=0: SUM / REPLACE on fp32 / bf16 through the axpby kernel). MAXLOC /
+        MINLOC: pair by pair, ``pairtype`` as in Comm.Allreduce. Atomic
         with respect to other Accumulates on the same target (exclusive target lock); blocking."""
-        from .comm import REPLACE, SUM
+        from .comm import MAXLOC, MINLOC, REPLACE, SUM
 
         op = op or SUM
+        if op is MAXLOC or op is MINLOC:
+            return self._pair_acc("Accumulate", op, pairtype, origin, None, target_rank, target_disp)
+        if pairtype is not None:
+            raise ValueError(f"Accumulate: pairtype goes with MAXLOC / MINLOC only, not with {op!r}")
         o = origin.contiguous().reshape(-1)
         codes = acc_codes("Accumulate", op, o.dtype)
         if codes is not None and self._plan_acc(o, None, target_rank, target_disp * self.disp_unit,
@@ -195,16 +222,23 @@ class Win:
         _dt.COUNTERS["rma_acc_runs"] += 1
 
     def Get_accumulate(self, origin: Optional[torch.Tensor], result: torch.Tensor, target_rank: int,
-                       target_disp: int = 0, op=None):
+                       target_disp: int = 0, op=None, pairtype=None):
         """result = target, then target = op(target, origin), element by element in one launch
         under the target's exclusive lock; complete on return. With NO_OP the origin may be None
         (an atomic Get). `result` is contiguous, of the target's element type and on the target
-        window's side, like the origin."""
-        from .comm import NO_OP, SUM
+        window's side, like the origin. MAXLOC / MINLOC: pair by pair, ``pairtype`` as in
+        Comm.Allreduce."""
+        from .comm import MAXLOC, MINLOC, NO_OP, SUM
 
         op = op or SUM
         if not result.is_contiguous():
             raise ValueError("Get_accumulate needs a contiguous result buffer")
+        if op is MAXLOC or op is MINLOC:
+            if origin is None:
+                raise ValueError("Get_accumulate: only NO_OP goes without an origin buffer")
+            return self._pair_acc("Get_accumulate", op, pairtype, origin, result, target_rank, target_disp)
+        if pairtype is not None:
+            raise ValueError(f"Get_accumulate: pairtype goes with MAXLOC / MINLOC only, not with {op!r}")
         if origin is None:
             if op is not NO_OP:
                 raise ValueError("Get_accumulate: only NO_OP goes without an origin buffer")
@@ -223,11 +257,21 @@ class Win:
         _dt.COUNTERS["rma_acc_kernel"] += 1
 
     def Fetch_and_op(self, origin: Optional[torch.Tensor], result: torch.Tensor, target_rank: int,
-                     target_disp: int = 0, op=None):
-        """Get_accumulate of one element (MPI_Fetch_and_op): counters, tickets, work queues."""
-        if result.numel() != 1 or (origin is not None and origin.numel() != 1):
+                     target_disp: int = 0, op=None, pairtype=None):
+        """Get_accumulate of one element (MPI_Fetch_and_op): counters, tickets, work queues. With
+        MAXLOC / MINLOC the element is one pair."""
+        from .comm import MAXLOC, MINLOC
+
+        if op is MAXLOC or op is MINLOC:
+            from .comm import _pair_layout
+
+            one = _pair_layout(pairtype, result.dtype).ext
+            if result.numel() * result.element_size() != one or origin is None or \
+                    origin.numel() * origin.element_size() != one:
+                raise ValueError("Fetch_and_op moves exactly one pair")
+        elif result.numel() != 1 or (origin is not None and origin.numel() != 1):
             raise ValueError("Fetch_and_op moves exactly one element")
-        self.Get_accumulate(origin, result, target_rank, target_disp, op)
+        self.Get_accumulate(origin, result, target_rank, target_disp, op, pairtype)
 
     # byte-addressed forms (the datatype-faithful Put / Get / Accumulate of mpiT.py): one
     # copy / accumulate per contiguous run of the target datatype
