@@ -16,6 +16,18 @@ using namespace mpit;
 namespace {
 hipStream_t S(uintptr_t s) { return reinterpret_cast<hipStream_t>(s); }
 py::tuple st_tuple(const Status& s) { return py::make_tuple(s.source, s.tag, s.error, s.count, s.cancelled); }
+// a layout as Python passes it to peer_plan_gather (loops, table, R, L, per) and, with the unit
+// and the span [lo, hi), to Window.pull_plan
+using Loops = std::vector<std::array<int64_t, 2>>;
+using SideTuple = std::tuple<Loops, uintptr_t, int64_t, int64_t, int64_t>;
+using PlanTuple = std::tuple<Loops, uintptr_t, int64_t, int64_t, int64_t, int, int64_t, int64_t>;
+PlanSide plan_side_of(uintptr_t base, const SideTuple& t) {
+  return PlanSide{base, std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t), std::get<4>(t)};
+}
+CopyPlan copy_plan_of(const PlanTuple& t) {
+  return CopyPlan{std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t),
+                  std::get<4>(t), std::get<5>(t), std::get<6>(t), std::get<7>(t)};
+}
 }  // namespace
 
 // the BN forward-finalize fold of a stats GEMM (gemm.hip stats_fold): None, or the tuple
@@ -637,6 +649,17 @@ PYBIND11_MODULE(_mpit, m) {
              return w.pull_gather(v, S(s));
            },
            py::arg("segs"), py::arg("stream"), py::call_guard<py::gil_scoped_release>())
+      // segs: [(member, byte offset in that member's window, source layout, local destination,
+      // destination layout)], a layout being (loops, table, R, L, per, unit, lo, hi) as in put_plan
+      .def("pull_plan",
+           [](Window& w, const std::vector<std::tuple<int, int64_t, PlanTuple, uintptr_t, PlanTuple>>& segs, uintptr_t s) {
+             std::vector<Window::PlanPull> v;
+             for (const auto& g : segs)
+               v.push_back({std::get<0>(g), std::get<1>(g), copy_plan_of(std::get<2>(g)), std::get<3>(g),
+                            copy_plan_of(std::get<4>(g))});
+             return w.pull_plan(v, S(s));
+           },
+           py::arg("segs"), py::arg("stream"), py::call_guard<py::gil_scoped_release>())
       .def("pull_fold",
            [](Window& w, int64_t off, int64_t nelem, int dtype, int op, uintptr_t dst, int m0, int m1, uintptr_t s) {
              return w.pull_fold(off, nelem, dtype, op, dst, m0, m1, S(s));
@@ -654,6 +677,20 @@ PYBIND11_MODULE(_mpit, m) {
       [](int dev, uintptr_t s, std::vector<uintptr_t> srcs, std::vector<uintptr_t> dsts, std::vector<int64_t> bytes,
          int max_blocks) { peer_gather(dev, S(s), srcs, dsts, bytes, max_blocks); },
       py::arg("dev"), py::arg("stream"), py::arg("srcs"), py::arg("dsts"), py::arg("bytes"), py::arg("max_blocks") = 0,
+      py::call_guard<py::gil_scoped_release>());
+  // segs: [(source address, source layout, destination address, destination layout, unit)], a
+  // layout being (loops, table, R, L, per)
+  m.def(
+      "peer_plan_gather",
+      [](int dev, uintptr_t s, const std::vector<std::tuple<uintptr_t, SideTuple, uintptr_t, SideTuple, int>>& segs,
+         int max_blocks, bool wide) {
+        std::vector<PlanSegment> v;
+        for (const auto& g : segs)
+          v.push_back({plan_side_of(std::get<0>(g), std::get<1>(g)), plan_side_of(std::get<2>(g), std::get<3>(g)),
+                       std::get<4>(g)});
+        peer_plan_gather(dev, S(s), v, max_blocks, wide);
+      },
+      py::arg("dev"), py::arg("stream"), py::arg("segs"), py::arg("max_blocks") = 0, py::arg("wide") = false,
       py::call_guard<py::gil_scoped_release>());
   m.def(
       "peer_fold",

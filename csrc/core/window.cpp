@@ -490,6 +490,47 @@ bool Window::pull_gather(const std::vector<PullSeg>& segs, hipStream_t s) {
   return true;
 }
 
+bool Window::pull_plan(const std::vector<PlanPull>& segs, hipStream_t s) {
+  if (!allreduce_capable()) return false;
+  if (segs.size() > size_t(kPeerMax)) throw std::invalid_argument("mpit: pull-plan takes up to 8 segments");
+  const int dev = device_ ? eng_.device() : -1;
+  self_member();
+  // the low bits of everything the host knows of a plan (the table's offsets are the caller's: p.unit)
+  auto bits_of = [](const CopyPlan& p) {
+    uint64_t b = uint64_t(p.L) | uint64_t(p.per) | uint64_t(p.unit);
+    for (const auto& l : p.loops)
+      if (l[0] > 1) b |= uint64_t(l[1]);
+    return b;
+  };
+  std::vector<PlanSegment> plan;
+  for (const PlanPull& g : segs) {
+    if (g.member < 0 || g.member >= int(remote_.size())) throw std::out_of_range("mpit: pull-plan member out of range");
+    const uintptr_t base = plan_base(g.member, g.off, g.src, "mpit: pull-plan source outside a member's window");
+    if (g.dstp.lo > g.dstp.hi) throw std::invalid_argument("mpit: pull-plan destination plan with lo > hi");
+    if ((base == 0) != (g.dstp.lo == g.dstp.hi))
+      throw std::invalid_argument("mpit: pull-plan: the two sides of a segment differ in packed size");
+    if (!base) continue;  // nothing to move
+    if (!g.dst) throw std::invalid_argument("mpit: pull-plan without a destination");
+    const uint64_t b = bits_of(g.src) | bits_of(g.dstp) | uint64_t(base) | uint64_t(g.dst) | 16u;
+    PlanSegment sg;
+    sg.src = PlanSide{base, g.src.loops, g.src.table, g.src.R, g.src.L, g.src.per};
+    sg.dst = PlanSide{g.dst, g.dstp.loops, g.dstp.table, g.dstp.R, g.dstp.L, g.dstp.per};
+    sg.unit = int(b & (~b + 1));
+    plan.push_back(std::move(sg));
+  }
+  peer_plan_check(plan);  // (throws here, never between the barriers)
+  auto drain = [&](const char* what) {
+    if (dev >= 0) hipw(hipStreamSynchronize(s), what);
+  };
+  if (dev >= 0) hipw(hipSetDevice(dev), "hipSetDevice");
+  drain("pull-plan B1");
+  sync();  // B1: every member's source is complete
+  if (!plan.empty()) peer_plan_gather(dev, s, plan);
+  drain("pull-plan B2");
+  sync();  // B2: every read of my window is finished
+  return true;
+}
+
 bool Window::pull_fold(int64_t off, int64_t nelem, int dtype, int op, uintptr_t dst, int m0, int m1, hipStream_t s) {
   if (!allreduce_capable() || !peer_reduce_supported(op, dtype)) return false;
   const int64_t es = peer_dtype_size(dtype);

@@ -127,6 +127,25 @@ class Window {
     int64_t bytes;
   };
   bool pull_gather(const std::vector<PullSeg>& segs, hipStream_t s);
+  // pull_plan: pull_gather between layouts, in one peer_plan_gather launch (kernels.h) for up to 8
+  // segments: the layout `src` at byte offset `off` of member `member`'s window to the layout
+  // `dstp` at the local address `dst` (Gatherv, Scatterv, Alltoallv, strided Alltoallw; a
+  // contiguous side is the one-run plan). The two layouts of a segment have the same packed size
+  // (std::invalid_argument) and the source span lies inside the member's window
+  // (std::out_of_range); both are checked, with all the kernel checks its arguments, before B1.
+  // The segment's unit is the largest power of two <= 16 dividing both base addresses, every
+  // stride, L and per of both sides and both plans' `unit` (what the caller knows to divide the
+  // offsets of their tables). An empty segment is dropped, as is my own window at the address and
+  // layout of `dst`; an empty list takes part in the barriers only. Tables are on this rank's
+  // device for a device window, in host memory for a host window (the host twin).
+  struct PlanPull {
+    int member;
+    int64_t off;
+    CopyPlan src;
+    uintptr_t dst;
+    CopyPlan dstp;
+  };
+  bool pull_plan(const std::vector<PlanPull>& segs, hipStream_t s);
   // pull_fold: dst[i] = fold over members [m0, m1) in member order of element i of the nelem
   // elements at byte offset `off` of their windows (reduce-scatter: every rank its own segment;
   // rooted reduce: the root alone). dst == 0 or nelem == 0: the barriers only.

@@ -452,6 +452,35 @@ void type_copy(int dev, hipStream_t s, int dir, uintptr_t strided, uintptr_t pac
                const std::vector<std::array<int64_t, 2>>& loops, uintptr_t table, int64_t R, int64_t L, int64_t per,
                int unit, int max_blocks = 0, bool wide = false);
 
+// ---- layout-to-layout gather of up to 8 segments (peer_plan.hip) --------------------------
+// The kernel of the irregular window collectives (Window::pull_plan). A side is a base address
+// plus a layout exactly as type_copy takes it (loops, table, R, L, per; a contiguous side is the
+// one-run layout: no loops, no table, R = 1, L = per = its bytes). For every packed byte q of
+// every segment g: dst_g[off_dst(q)] = src_g[off_src(q)], packed order as in type_copy. `unit` (a
+// power of two <= 16) divides every offset, length, stride and the base address of BOTH sides of
+// its segment: one lane moves one unit per access. One launch on `s` for all segments together
+// (blocks find their segment in a prefix table of tile counts), or the host twin for dev < 0.
+// std::invalid_argument, before any launch: more than 8 segments, sides of unequal packed size,
+// and what type_copy refuses of either side. Dropped: zero-length segments and segments whose two
+// sides are the same address and layout. Destinations are disjoint from each other and from
+// every source. Run tables up to 1,024 runs are staged in LDS, longer ones read from global
+// memory. max_blocks and wide as in type_copy (64-bit indices by themselves when a segment packs
+// 4 GiB or more). The layouts are trusted. Allocates and synchronises nothing; no atomics, no
+// cross-rank communication. peer_plan_check makes the checks alone.
+struct PlanSide {
+  uintptr_t base;
+  std::vector<std::array<int64_t, 2>> loops;
+  uintptr_t table;
+  int64_t R, L, per;
+};
+struct PlanSegment {
+  PlanSide src, dst;
+  int unit;
+};
+void peer_plan_check(const std::vector<PlanSegment>& segs);
+void peer_plan_gather(int dev, hipStream_t s, const std::vector<PlanSegment>& segs, int max_blocks = 0,
+                      bool wide = false);
+
 // ---- one-sided accumulate on a derived-datatype layout (type_acc.hip) --------------------
 // For every element e of the layout (type_copy's: loops, table, R, L, per, unit; the same run
 // modes, index widths, max_blocks and wide), in one launch on `s`, or the host twin for dev < 0:

@@ -603,6 +603,13 @@ def _pr_codes(op: Op, dtype: torch.dtype):
 
 # the collectives with a window path (Comm.coll_stats keys)
 _WIN_COLLS = ("reduce_scatter", "allgather", "alltoall", "bcast", "reduce", "scan", "exscan")
+# the irregular collectives with a window path (Comm.vcoll_stats keys)
+_WIN_VCOLLS = ("gatherv", "scatterv", "alltoallv", "alltoallw")
+# what a member may find wrong with its own buffers (published in the descriptor exchange)
+_VCOLL_ERRORS = {1: "a count / displacement pair lies outside its buffer",
+                 2: "a tensor needs more than three loops (or has a negative stride)",
+                 3: "a destination overlaps a source that is not this rank's own in-place part",
+                 4: "a destination tensor has a zero or overlapping stride"}
 
 
 class _SymRec:
@@ -665,6 +672,7 @@ class Comm:
         self._ar_calls = {"window": 0, "window_staged": 0, "p2p": 0, "rccl": 0}
         self._ar_off = False  # a member cannot run Window::allreduce: "window" falls back (agreed)
         self._coll_calls = {c: {"window": 0, "window_staged": 0, "fallback": 0} for c in _WIN_COLLS}
+        self._vcoll_calls = {c: {"window": 0, "window_staged": 0, "fallback": 0} for c in _WIN_VCOLLS}
 
     # ---------------------------------------------------------------- basics
     def Get_rank(self) -> int:
@@ -1201,11 +1209,14 @@ class Comm:
             return False
         return bool(native().peer_reduce_supported(code, dt))
 
+    @staticmethod
+    def _ar_stage_bytes() -> int:
+        return max(4096, int(float(os.environ.get("MPIT_AR_STAGE_MB", "32")) * (1 << 20))) & ~15
+
     def _ar_staging(self, kind: str) -> torch.Tensor:
         st = self._ar_stage.get(kind)
         if st is None:
-            nb = max(4096, int(float(os.environ.get("MPIT_AR_STAGE_MB", "32")) * (1 << 20))) & ~15
-            st = self._ar_stage[kind] = self.sym_alloc(nb, torch.uint8, device=(kind == "cuda"))
+            st = self._ar_stage[kind] = self.sym_alloc(self._ar_stage_bytes(), torch.uint8, device=(kind == "cuda"))
         return st
 
     def _ar_submit(self, src: torch.Tensor, dst: torch.Tensor, op: Op, keep=()) -> Request:
@@ -1353,7 +1364,7 @@ class Comm:
 
     def _coll_count(self, name: str, path: str):
         with self._ar_lock:
-            self._coll_calls[name][path] += 1
+            (self._coll_calls if name in self._coll_calls else self._vcoll_calls)[name][path] += 1
 
     @staticmethod
     def _addr(t: torch.Tensor) -> int:
@@ -1644,6 +1655,195 @@ class Comm:
                         dst[i: i + m].copy_(sv)
         return self._coll_submit(name, hit is None, fn, src, keep)
 
+    # ---------------------------------------------------------------- irregular window collectives
+    # Gatherv / Gather, Scatterv / Scatter, Alltoallv and Alltoallw with ``algo="window"``: a rank
+    # cannot know a peer's displacements, counts or tensor layouts, so every member first publishes
+    # them: one fixed-size int64 record per member (a header and, per peer, where the segment sent
+    # to it lies: the symmetric range and byte offset, the bytes, the loops and run length of
+    # :func:`datatypes.layout_of`, plus the bytes expected from that peer), exchanged in ONE host
+    # Allgather (``algo="auto"``) on the caller's thread before any ticket. Every decision and
+    # every refusal is taken from the exchanged records alone, so all members take the same path
+    # or raise the same ValueError, and nobody is left waiting in the protocol's barrier.
+    # Paths: *in place* when every non-empty send segment lies in one symmetric range (peers read
+    # it where it lies: Window::pull_gather when every segment of the call is contiguous,
+    # Window::pull_plan, one peer_plan_gather launch, csrc/kernels/peer_plan.hip, as soon as one is
+    # strided; a rank's own part is a local segment of the same launch); *staged* when not and
+    # every member's send stream (each segment padded to 16 bytes) fits the staging window
+    # (MPIT_AR_STAGE_MB), packed there in one piece by type_copy; else the *fallback*, today's
+    # routing, on every member alike. Gatherv: the root alone pulls; Scatterv: every rank pulls its
+    # piece from the root. ``sendbuf`` is never modified. Counted in :meth:`vcoll_stats`.
+    _VREC = 12  # int64 per send record: range, offset, bytes, loop count, 3 x (n, stride), run length, spare
+
+    def vcoll_stats(self) -> dict:
+        """Calls with ``algo="window"`` of Gatherv / Gather (``gatherv``), Scatterv / Scatter
+        (``scatterv``), ``alltoallv`` and ``alltoallw``: ``window`` (of which ``window_staged`` went
+        through the staging buffer) and ``fallback`` (not eligible: today's routing)."""
+        with self._ar_lock:
+            return {k: dict(v) for k, v in self._vcoll_calls.items()}
+
+    def _vcoll_span(self, buf: torch.Tensor, displ, count):
+        """buf[displ: displ + count], or None when that lies outside buf (a slice would clamp)."""
+        displ, count = int(displ), int(count)
+        if displ < 0 or count < 0 or displ + count > buf.numel():
+            return None
+        return buf[displ: displ + count]
+
+    def _vcoll(self, name: str, sends, recvs, err: int, keep=()) -> Optional[Request]:
+        """``sends[q]`` / ``recvs[q]``: the tensor (any strides) this rank sends to / receives from
+        member q, or None for nothing; ``err``: a _VCOLL_ERRORS code the caller found. A Request, or
+        None on every member alike (the fallback)."""
+        from .datatypes import layout_of, run_plan, _bytes_at
+
+        n, me, V = self.Get_size(), self.Get_rank(), self._VREC
+        if not (2 <= n <= 8 and self._rank != UNDEFINED and not self._ar_off):
+            self._coll_count(name, "fallback")
+            return None
+        tensors = [t for t in list(sends) + list(recvs) if t is not None]
+        ok = all(t.device == tensors[0].device for t in tensors)
+        ok = ok and all(not t.is_cuda or t.device == _rt.device() for t in tensors)
+        kind = 0 if not tensors else (2 if tensors[0].is_cuda else 1)
+        # ---- my record
+        rec = torch.zeros(4 + (V + 1) * n, dtype=torch.int64)
+        splans, rplans, spans = [None] * n, [None] * n, []
+        for q in range(n):
+            for side, t in ((0, sends[q]), (1, recvs[q])):
+                if t is None or t.numel() == 0:
+                    continue
+                try:
+                    plan = layout_of(t)
+                except ValueError:
+                    err = err or 2
+                    continue
+                addr = self._addr(t)
+                spans.append((side, q, addr, addr + plan.hi, plan.loops, plan.L))
+                if side == 1:
+                    if plan.self_overlap():
+                        err = err or 4
+                    rplans[q] = (addr, plan)
+                    rec[4 + V * n + q] = plan.total
+                    rec[3] |= int(bool(plan.loops))
+                    continue
+                splans[q] = plan
+                sym = -1
+                for k, sr in enumerate(self._sym):
+                    if sr.lo <= addr and addr + plan.hi <= sr.hi and sr.tensor.device == t.device:
+                        sym, addr = k, addr - sr.lo
+                        break
+                loops = [x for ns in plan.loops for x in ns] + [0] * (6 - 2 * len(plan.loops))
+                rec[4 + V * q: 4 + V * (q + 1)] = torch.tensor([sym, addr if sym >= 0 else 0, plan.total, len(plan.loops)]
+                                                              + loops + [plan.L, 0])
+        for _, qd, dlo, dhi, dloops, dl in (x for x in spans if x[0] == 1):
+            for _, qs, slo, shi, sloops, sl in (x for x in spans if x[0] == 0):
+                own = qd == me and qs == me and dlo == slo and dloops == sloops and dl == sl
+                if dlo < shi and slo < dhi and not own:
+                    err = err or 3
+        rec[0], rec[1], rec[2] = err, int(ok), kind
+        # ---- the exchange, and what every member reads from it alike
+        every = torch.zeros(n * rec.numel(), dtype=torch.int64)
+        self.Allgather(rec, every, algo="auto")
+        every = every.view(n, -1).tolist()
+        kinds = {m[2] for m in every if m[2]}
+        if not all(m[1] for m in every) or len(kinds) > 1:
+            self._coll_count(name, "fallback")
+            return None
+        for s, m in enumerate(every):
+            if m[0]:
+                raise ValueError(f"{name}(algo='window'): rank {s}: {_VCOLL_ERRORS.get(m[0], m[0])}")
+        S = [[m[4 + V * q: 4 + V * (q + 1)] for q in range(n)] for m in every]  # S[s][q]: s sends to q
+        for s in range(n):
+            for q in range(n):
+                if S[s][q][2] != every[q][4 + V * n + s]:
+                    raise ValueError(f"{name}(algo='window'): rank {s} sends {S[s][q][2]} bytes to rank {q}, "
+                                     f"which expects {every[q][4 + V * n + s]}")
+        cuda = kinds == {2}
+        like = tensors[0] if tensors else torch.empty(0, device=_rt.device() if cuda else "cpu")
+        live = [S[s][q] for s in range(n) for q in range(n) if S[s][q][2]]
+        ranges = {r[0] for r in live}
+        strided_recv = any(m[3] for m in every)
+        staged = not live or len(ranges) != 1 or -1 in ranges
+        if staged:
+            # member s's stream: its segments in peer order, each padded to 16 bytes
+            soff = [[sum((S[s][p][2] + 15) & ~15 for p in range(q)) for q in range(n + 1)] for s in range(n)]
+            if max(o[n] for o in soff) > self._ar_stage_bytes():
+                self._coll_count(name, "fallback")
+                return None
+            stage = self._coll_stage(name, like)
+            if stage is None:
+                return None
+            win, st = stage
+            use_plan = strided_recv
+        else:
+            win, st = self._sym[ranges.pop()].win._w, None
+            use_plan = strided_recv or any(r[3] for r in live)
+        # ---- what this rank pulls: from member s, the segment it sends to me
+        segs = []
+        for s in range(n):
+            r = S[s][me]
+            if not r[2]:
+                continue
+            dst, dplan = rplans[s]
+            if staged:
+                off, sloops, sl = soff[s][me], [], r[2]
+            else:
+                off, sloops, sl = r[1], [[r[4 + 2 * k], r[5 + 2 * k]] for k in range(r[3])], r[10]
+            if use_plan:
+                shi = sl + sum((a - 1) * b for a, b in sloops)
+                segs.append((s, off, (sloops, 0, 1, sl, sl, 16, 0, shi), dst,
+                             ([list(x) for x in dplan.loops], 0, 1, dplan.L, dplan.L, 16, 0, dplan.hi)))
+            else:
+                segs.append((s, off, dst, r[2]))
+
+        def fn(sptr, stream):
+            if staged:
+                for q in range(n):
+                    if splans[q] is not None:  # pack (or copy) my segment for q into my stream
+                        run_plan(splans[q], 0, _bytes_at(sends[q]), st[soff[me][q]: soff[me][q] + splans[q].total])
+            self._coll_done(win.pull_plan(segs, sptr) if use_plan else win.pull_gather(segs, sptr))
+        return self._coll_submit(name, staged, fn, like, keep)
+
+    def _vcoll_gatherv(self, src, recvbuf, counts, displs, root, keep=()) -> Optional[Request]:
+        n, me = self.Get_size(), self.Get_rank()
+        sends, recvs, err = [None] * n, [None] * n, 0
+        if me != root:
+            sends[root] = src
+        else:
+            dst = _flat(recvbuf)
+            if counts is None:
+                counts = [src.numel()] * n
+            if displs is None:
+                displs = [sum(counts[:i]) for i in range(n)]
+            for q in range(n):
+                recvs[q] = self._vcoll_span(dst, displs[q], counts[q])
+                err = err or int(recvs[q] is None)
+            sends[me] = self._vcoll_span(src, 0, counts[me])
+            err = err or int(sends[me] is None)
+        return self._vcoll("gatherv", sends, recvs, err, keep)
+
+    def _vcoll_scatterv(self, sendbuf, dst, counts, displs, root, keep=()) -> Optional[Request]:
+        n, me = self.Get_size(), self.Get_rank()
+        sends, recvs, err = [None] * n, [None] * n, 0
+        if me != root:
+            recvs[root] = dst
+        else:
+            src = _flat(sendbuf)
+            if counts is None:
+                counts = [dst.numel()] * n
+            if displs is None:
+                displs = [sum(counts[:i]) for i in range(n)]
+            for q in range(n):
+                sends[q] = self._vcoll_span(src, displs[q], counts[q])
+                err = err or int(sends[q] is None)
+            recvs[me] = self._vcoll_span(dst, 0, counts[me])
+            err = err or int(recvs[me] is None)
+        return self._vcoll("scatterv", sends, recvs, err, keep)
+
+    def _vcoll_alltoallv(self, src, sendcounts, sdispls, dst, recvcounts, rdispls, keep=()) -> Optional[Request]:
+        n = self.Get_size()
+        sends = [self._vcoll_span(src, sdispls[q], sendcounts[q]) for q in range(n)]
+        recvs = [self._vcoll_span(dst, rdispls[q], recvcounts[q]) for q in range(n)]
+        err = int(any(t is None for t in sends + recvs))
+        return self._vcoll("alltoallv", sends, recvs, err, keep)
+
     def _bg(self, fn, keep=()) -> Request:
         req = Request(self, keep=keep)
         with _coll_cv:
@@ -1722,9 +1922,16 @@ class Comm:
         return self._bg(lambda: self.Reduce_scatter(sendbuf, recvbuf, recvcounts, op, algo=fb),
                         keep=(sendbuf, recvbuf))
 
-    def Gatherv(self, sendbuf, recvbuf, counts: Optional[Sequence[int]] = None, displs=None, root: int = 0):
+    def Gatherv(self, sendbuf, recvbuf, counts: Optional[Sequence[int]] = None, displs=None, root: int = 0,
+                algo: Optional[str] = None):
+        """``algo``: see "irregular window collectives" above (None: the MPIT_COLLECTIVES variable)."""
         n, me = self.Get_size(), self.Get_rank()
         src = _flat(sendbuf)
+        if self._coll_algo(algo) == "window":
+            req = self._vcoll_gatherv(src, recvbuf, counts, displs, root, keep=(sendbuf, recvbuf))
+            if req is not None:
+                req.Wait()
+                return recvbuf
         if me != root:
             self._csend(src, root, 3).Wait()
             return recvbuf
@@ -1743,12 +1950,19 @@ class Comm:
         Request.Waitall(reqs)
         return recvbuf
 
-    def Gather(self, sendbuf, recvbuf, root: int = 0):
-        return self.Gatherv(sendbuf, recvbuf, None, None, root)
+    def Gather(self, sendbuf, recvbuf, root: int = 0, algo: Optional[str] = None):
+        return self.Gatherv(sendbuf, recvbuf, None, None, root, algo=algo)
 
-    def Scatterv(self, sendbuf, recvbuf, counts: Optional[Sequence[int]] = None, displs=None, root: int = 0):
+    def Scatterv(self, sendbuf, recvbuf, counts: Optional[Sequence[int]] = None, displs=None, root: int = 0,
+                 algo: Optional[str] = None):
+        """``algo``: see "irregular window collectives" above (None: the MPIT_COLLECTIVES variable)."""
         n, me = self.Get_size(), self.Get_rank()
         dst = _flat(recvbuf)
+        if self._coll_algo(algo) == "window":
+            req = self._vcoll_scatterv(sendbuf, dst, counts, displs, root, keep=(sendbuf, recvbuf))
+            if req is not None:
+                req.Wait()
+                return recvbuf
         if me != root:
             self._crecv(dst, root, 4).Wait()
             return recvbuf
@@ -1767,8 +1981,8 @@ class Comm:
         Request.Waitall(reqs)
         return recvbuf
 
-    def Scatter(self, sendbuf, recvbuf, root: int = 0):
-        return self.Scatterv(sendbuf, recvbuf, None, None, root)
+    def Scatter(self, sendbuf, recvbuf, root: int = 0, algo: Optional[str] = None):
+        return self.Scatterv(sendbuf, recvbuf, None, None, root, algo=algo)
 
     def Allgatherv(self, sendbuf, recvbuf, counts: Optional[Sequence[int]] = None, displs=None,
                    algo: Optional[str] = None):
@@ -1791,16 +2005,22 @@ class Comm:
             counts = [src.numel()] * n
         if displs is None:
             displs = [sum(counts[:i]) for i in range(n)]
-        self.Gatherv(src, dst, counts, displs, 0)
+        self.Gatherv(src, dst, counts, displs, 0, algo="auto")
         self.Bcast(dst, 0, algo="auto")
         return recvbuf
 
     def Allgather(self, sendbuf, recvbuf, algo: Optional[str] = None):
         return self.Allgatherv(sendbuf, recvbuf, None, None, algo=algo)
 
-    def Alltoallv(self, sendbuf, sendcounts, sdispls, recvbuf, recvcounts, rdispls):
+    def Alltoallv(self, sendbuf, sendcounts, sdispls, recvbuf, recvcounts, rdispls, algo: Optional[str] = None):
+        """``algo``: see "irregular window collectives" above (None: the MPIT_COLLECTIVES variable)."""
         n, me = self.Get_size(), self.Get_rank()
         src, dst = _flat(sendbuf), _flat(recvbuf)
+        if self._coll_algo(algo) == "window":
+            req = self._vcoll_alltoallv(src, sendcounts, sdispls, dst, recvcounts, rdispls, keep=(sendbuf, recvbuf))
+            if req is not None:
+                req.Wait()
+                return recvbuf
         reqs = []
         for q in range(n):
             rseg = dst[rdispls[q]: rdispls[q] + recvcounts[q]]
@@ -1830,11 +2050,19 @@ class Comm:
             return recvbuf
         c = src.numel() // n
         d = [i * c for i in range(n)]
-        return self.Alltoallv(src, [c] * n, d, dst, [c] * n, d)
+        return self.Alltoallv(src, [c] * n, d, dst, [c] * n, d, algo="auto")
 
-    def Alltoallw(self, sendbufs: Sequence[torch.Tensor], recvbufs: Sequence[torch.Tensor]):
-        """Per-peer tensors of arbitrary dtype/shape (MPI_Alltoallw's per-peer types)."""
+    def Alltoallw(self, sendbufs: Sequence[torch.Tensor], recvbufs: Sequence[torch.Tensor],
+                  algo: Optional[str] = None):
+        """Per-peer tensors of arbitrary dtype/shape (MPI_Alltoallw's per-peer types). ``algo``: see
+        "irregular window collectives" above (None: the MPIT_COLLECTIVES variable); by window the
+        tensors may have any strides within three loops and are moved layout to layout."""
         n, me = self.Get_size(), self.Get_rank()
+        if self._coll_algo(algo) == "window":
+            req = self._vcoll("alltoallw", list(sendbufs), list(recvbufs), 0, keep=(sendbufs, recvbufs))
+            if req is not None:
+                req.Wait()
+                return recvbufs
         reqs = []
         for q in range(n):
             if q == me:
@@ -1868,7 +2096,7 @@ class Comm:
         tmp = torch.empty_like(src) if self.Get_rank() == 0 else None
         self.Reduce(src, tmp if tmp is not None else src, op, 0, algo="auto")
         displs = [sum(recvcounts[:i]) for i in range(n)]
-        self.Scatterv(tmp, dst, recvcounts, displs, 0)
+        self.Scatterv(tmp, dst, recvcounts, displs, 0, algo="auto")
         return recvbuf
 
     @_pair_call
