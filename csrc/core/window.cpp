@@ -378,75 +378,93 @@ bool Window::allreduce_capable() const {
   return true;
 }
 
+// The epoch every window collective runs its one launch in. Between the two barriers nothing may
+// throw (a rank that left would leave the others waiting): the callers validate their arguments
+// and throw before they come here, and `launch(dev)` does not throw on validated arguments.
+void Window::epoch(hipStream_t s, const char* what, const std::function<void(int)>& launch) {
+  const int dev = device_ ? eng_.device() : -1;
+  auto drain = [&](const char* barrier) {
+    if (dev >= 0) hipw(hipStreamSynchronize(s), (std::string(what) + barrier).c_str());
+  };
+  if (dev >= 0) hipw(hipSetDevice(dev), "hipSetDevice");
+  drain(" B1");
+  sync();  // B1: every member's input is complete
+  launch(dev);
+  drain(" B2");
+  sync();  // B2: every result has landed at its owner and every read of my memory is finished
+}
+
+// Bound k of the n slices of nelem elements at byte offset off (two-shot all-reduce, scan).
+// Interior bounds are rounded down to a 16-B address of member 0's range, from the alignment
+// member 0 published in its blob (checked against every mapping at connect), so every rank
+// computes the same bounds. They count elements, so a slice never starts inside a pair.
+int64_t Window::slice_bounds(int k, int n, int64_t nelem, int64_t off, int64_t es) const {
+  if (k <= 0) return 0;
+  if (k >= n) return nelem;
+  const int64_t b = nelem * k / n;
+  const int64_t a = ((int64_t(remote_[0].align) + off + b * es) & 15) / es;
+  return std::max<int64_t>(0, b - a);
+}
+
+// a reducing collective's range: aligned for dtype ...
+void Window::check_range_aligned(const char* who, int64_t off, int64_t nelem, int dtype) const {
+  if (off < 0 || nelem < 0 || off % peer_dtype_align(dtype))
+    throw std::invalid_argument(std::string("mpit: ") + who + " range misaligned");
+}
+
+// ... and inside the window of every member in [m0, m1)
+void Window::check_range_inside(const char* who, int64_t off, int64_t nelem, int dtype, int m0, int m1) const {
+  for (int m = m0; m < m1; ++m)
+    if (off + nelem * peer_dtype_size(dtype) > remote_[size_t(m)].bytes)
+      throw std::out_of_range(std::string("mpit: ") + who + " range outside a member's window");
+}
+
+std::vector<uintptr_t> Window::member_ptrs(int64_t off, int m0, int m1) const {
+  std::vector<uintptr_t> p;
+  for (int m = m0; m < m1; ++m) p.push_back(reinterpret_cast<uintptr_t>(remote_[size_t(m)].ptr) + uintptr_t(off));
+  return p;
+}
+
 bool Window::allreduce(int64_t off, int64_t nelem, int dtype, int op, hipStream_t s, int mode, uintptr_t dst) {
   if (!allreduce_capable() || !peer_reduce_supported(op, dtype)) return false;
   const int64_t es = peer_dtype_size(dtype);  // a pair type: nelem counts pairs, es is the pair's extent
   const int n = int(remote_.size());
-  if (off < 0 || nelem < 0 || off % peer_dtype_align(dtype))
-    throw std::invalid_argument("mpit: window all-reduce range misaligned");
-  for (const Remote& r : remote_)
-    if (off + nelem * es > r.bytes) throw std::out_of_range("mpit: all-reduce range outside a member's window");
+  check_range_aligned("window all-reduce", off, nelem, dtype);
+  check_range_inside("all-reduce", off, nelem, dtype, 0, n);
   const int dev = device_ ? eng_.device() : -1;
-  auto drain = [&](const char* what) {
-    if (dev >= 0) hipw(hipStreamSynchronize(s), what);
-  };
-  if (dev >= 0) hipw(hipSetDevice(dev), "hipSetDevice");
-  int me = -1;
-  std::vector<uintptr_t> ptrs(static_cast<size_t>(n));
-  for (int m = 0; m < n; ++m) {
-    ptrs[size_t(m)] = reinterpret_cast<uintptr_t>(remote_[size_t(m)].ptr) + uintptr_t(off);
-    if (remote_[size_t(m)].ctl == ctl_) me = m;
-  }
-  if (me < 0) throw std::runtime_error("mpit: window all-reduce on a rank that is no member");
+  const int me = self_member("all-reduce");
   const bool oneshot = dst != 0 || mode == kArOneShot || (mode == kArAuto && nelem * es <= oneshot_bytes());
-  drain("all-reduce B1");
-  sync();  // B1: every member's input is complete
-  if (nelem > 0 && !oneshot) {
-    // two-shot push: rank r reduces slice r from all members and stores it into all members.
-    // Interior bounds rounded down to a 16-B address of member 0's range, from the alignment
-    // member 0 published in its blob (checked against every mapping at connect), so every
-    // rank computes the same bounds. They count elements, so a slice never starts inside a pair.
-    auto bound = [&](int k) -> int64_t {
-      if (k <= 0) return 0;
-      if (k >= n) return nelem;
-      const int64_t b = nelem * k / n;
-      const int64_t a = ((int64_t(remote_[0].align) + off + b * es) & 15) / es;
-      return std::max<int64_t>(0, b - a);
-    };
-    const int64_t lo = bound(me), hi = bound(me + 1);
-    if (hi > lo) {
-      std::vector<uintptr_t> sl(ptrs);
-      for (auto& p : sl) p += uintptr_t(lo * es);
-      peer_reduce(dev, s, op, dtype, sl, sl, hi - lo);
-    }
-  } else if (nelem > 0) {
-    // one-shot: every rank reduces the whole range. My window must stay as it is until B2 (a
-    // slower peer may still be reading it): the result goes to `dst`, or to a private buffer
-    // copied back after B2.
-    uintptr_t out = dst;
-    if (!out) {
-      if (ar_tmp_bytes_ < nelem * es) {
-        if (ar_tmp_) {
-          if (dev >= 0) hipw(hipFree(ar_tmp_), "hipFree(all-reduce tmp)");
-          else std::free(ar_tmp_);
-          ar_tmp_ = nullptr;
-        }
-        const int64_t cap = std::max<int64_t>(nelem * es, 64 << 10);
-        if (dev >= 0) hipw(hipMalloc(&ar_tmp_, size_t(cap)), "hipMalloc(all-reduce tmp)");
-        else if (!(ar_tmp_ = std::malloc(size_t(cap)))) throw std::bad_alloc();
-        ar_tmp_bytes_ = cap;
+  // two-shot push: rank r reduces slice r (slice_bounds) from all members and stores it into all
+  // members. One-shot: every rank reduces the whole range. My window must stay as it is until B2
+  // (a slower peer may still be reading it): the result goes to `dst`, or to a private buffer
+  // copied back after B2.
+  const int64_t lo = oneshot ? 0 : slice_bounds(me, n, nelem, off, es);
+  const int64_t hi = oneshot ? nelem : slice_bounds(me + 1, n, nelem, off, es);
+  const std::vector<uintptr_t> srcs = member_ptrs(off + lo * es, 0, n);
+  std::vector<uintptr_t> dsts = srcs;
+  if (oneshot && nelem > 0) {
+    if (!dst && ar_tmp_bytes_ < nelem * es) {  // (before B1: nothing throws between the barriers)
+      if (dev >= 0) hipw(hipSetDevice(dev), "hipSetDevice");
+      if (ar_tmp_) {
+        if (dev >= 0) hipw(hipFree(ar_tmp_), "hipFree(all-reduce tmp)");
+        else std::free(ar_tmp_);
+        ar_tmp_ = nullptr;
       }
-      out = reinterpret_cast<uintptr_t>(ar_tmp_);
+      const int64_t cap = std::max<int64_t>(nelem * es, 64 << 10);
+      if (dev >= 0) hipw(hipMalloc(&ar_tmp_, size_t(cap)), "hipMalloc(all-reduce tmp)");
+      else if (!(ar_tmp_ = std::malloc(size_t(cap)))) throw std::bad_alloc();
+      ar_tmp_bytes_ = cap;
     }
-    peer_reduce(dev, s, op, dtype, ptrs, {out}, nelem);
+    dsts = {dst ? dst : reinterpret_cast<uintptr_t>(ar_tmp_)};
   }
-  drain("all-reduce B2");
-  sync();  // B2: every slice has landed everywhere and every read of my memory is finished
+  epoch(s, "all-reduce", [&](int d) {
+    if (hi > lo) peer_reduce(d, s, op, dtype, srcs, dsts, hi - lo);
+  });
   if (nelem > 0 && oneshot && !dst) {
-    void* mine = reinterpret_cast<void*>(ptrs[size_t(me)]);
+    void* mine = reinterpret_cast<void*>(srcs[size_t(me)]);
     if (dev >= 0) {
       hipw(hipMemcpyAsync(mine, ar_tmp_, size_t(nelem * es), hipMemcpyDeviceToDevice, s), "all-reduce copy back");
-      drain("all-reduce copy back");
+      hipw(hipStreamSynchronize(s), "all-reduce copy back");
     } else {
       std::memcpy(mine, ar_tmp_, size_t(nelem * es));
     }
@@ -454,16 +472,15 @@ bool Window::allreduce(int64_t off, int64_t nelem, int dtype, int op, hipStream_
   return true;
 }
 
-int Window::self_member() const {
+int Window::self_member(const char* who) const {
   for (size_t m = 0; m < remote_.size(); ++m)
     if (remote_[m].ctl == ctl_) return int(m);
-  throw std::runtime_error("mpit: window collective on a rank that is no member");
+  throw std::runtime_error(std::string("mpit: window ") + who + " on a rank that is no member");
 }
 
 bool Window::pull_gather(const std::vector<PullSeg>& segs, hipStream_t s) {
   if (!allreduce_capable()) return false;
   if (segs.size() > size_t(kPeerMax)) throw std::invalid_argument("mpit: pull-gather takes up to 8 segments");
-  const int dev = device_ ? eng_.device() : -1;
   self_member();
   std::vector<uintptr_t> srcs, dsts;
   std::vector<int64_t> bytes;
@@ -478,22 +495,15 @@ bool Window::pull_gather(const std::vector<PullSeg>& segs, hipStream_t s) {
     dsts.push_back(g.dst);
     bytes.push_back(g.bytes);
   }
-  auto drain = [&](const char* what) {
-    if (dev >= 0) hipw(hipStreamSynchronize(s), what);
-  };
-  if (dev >= 0) hipw(hipSetDevice(dev), "hipSetDevice");
-  drain("pull-gather B1");
-  sync();  // B1: every member's source is complete
-  if (!srcs.empty()) peer_gather(dev, s, srcs, dsts, bytes);
-  drain("pull-gather B2");
-  sync();  // B2: every read of my window is finished
+  epoch(s, "pull-gather", [&](int dev) {
+    if (!srcs.empty()) peer_gather(dev, s, srcs, dsts, bytes);
+  });
   return true;
 }
 
 bool Window::pull_plan(const std::vector<PlanPull>& segs, hipStream_t s) {
   if (!allreduce_capable()) return false;
   if (segs.size() > size_t(kPeerMax)) throw std::invalid_argument("mpit: pull-plan takes up to 8 segments");
-  const int dev = device_ ? eng_.device() : -1;
   self_member();
   // the low bits of everything the host knows of a plan (the table's offsets are the caller's: p.unit)
   auto bits_of = [](const CopyPlan& p) {
@@ -519,45 +529,24 @@ bool Window::pull_plan(const std::vector<PlanPull>& segs, hipStream_t s) {
     plan.push_back(std::move(sg));
   }
   peer_plan_check(plan);  // (throws here, never between the barriers)
-  auto drain = [&](const char* what) {
-    if (dev >= 0) hipw(hipStreamSynchronize(s), what);
-  };
-  if (dev >= 0) hipw(hipSetDevice(dev), "hipSetDevice");
-  drain("pull-plan B1");
-  sync();  // B1: every member's source is complete
-  if (!plan.empty()) peer_plan_gather(dev, s, plan);
-  drain("pull-plan B2");
-  sync();  // B2: every read of my window is finished
+  epoch(s, "pull-plan", [&](int dev) {
+    if (!plan.empty()) peer_plan_gather(dev, s, plan);
+  });
   return true;
 }
 
 bool Window::pull_fold(int64_t off, int64_t nelem, int dtype, int op, uintptr_t dst, int m0, int m1, hipStream_t s) {
   if (!allreduce_capable() || !peer_reduce_supported(op, dtype)) return false;
-  const int64_t es = peer_dtype_size(dtype);
-  const int n = int(remote_.size());
-  if (off < 0 || nelem < 0 || off % peer_dtype_align(dtype))
-    throw std::invalid_argument("mpit: pull-fold range misaligned");
-  if (m0 < 0 || m1 > n || m0 >= m1) throw std::out_of_range("mpit: pull-fold member range");
+  check_range_aligned("pull-fold", off, nelem, dtype);
+  if (m0 < 0 || m1 > int(remote_.size()) || m0 >= m1) throw std::out_of_range("mpit: pull-fold member range");
   if (dst % uintptr_t(peer_dtype_align(dtype))) throw std::invalid_argument("mpit: pull-fold destination misaligned");
-  const int dev = device_ ? eng_.device() : -1;
   self_member();
-  std::vector<uintptr_t> srcs;
-  if (dst && nelem > 0) {
-    for (int m = m0; m < m1; ++m) {
-      if (off + nelem * es > remote_[size_t(m)].bytes)
-        throw std::out_of_range("mpit: pull-fold range outside a member's window");
-      srcs.push_back(reinterpret_cast<uintptr_t>(remote_[size_t(m)].ptr) + uintptr_t(off));
-    }
-  }
-  auto drain = [&](const char* what) {
-    if (dev >= 0) hipw(hipStreamSynchronize(s), what);
-  };
-  if (dev >= 0) hipw(hipSetDevice(dev), "hipSetDevice");
-  drain("pull-fold B1");
-  sync();  // B1: every member's input is complete
-  if (!srcs.empty()) peer_fold(dev, s, op, dtype, srcs, dst, nelem);
-  drain("pull-fold B2");
-  sync();  // B2: every read of my window is finished
+  const bool reads = dst && nelem > 0;  // otherwise this rank only keeps the epoch: no member is read
+  if (reads) check_range_inside("pull-fold", off, nelem, dtype, m0, m1);
+  const std::vector<uintptr_t> srcs = member_ptrs(off, m0, reads ? m1 : m0);
+  epoch(s, "pull-fold", [&](int dev) {
+    if (!srcs.empty()) peer_fold(dev, s, op, dtype, srcs, dst, nelem);
+  });
   return true;
 }
 
@@ -565,38 +554,15 @@ bool Window::scan(int64_t off, int64_t nelem, int dtype, int op, bool exclusive,
   if (!allreduce_capable() || !peer_reduce_supported(op, dtype)) return false;
   const int64_t es = peer_dtype_size(dtype);
   const int n = int(remote_.size());
-  if (off < 0 || nelem < 0 || off % peer_dtype_align(dtype))
-    throw std::invalid_argument("mpit: window scan range misaligned");
-  for (const Remote& r : remote_)
-    if (off + nelem * es > r.bytes) throw std::out_of_range("mpit: scan range outside a member's window");
-  const int dev = device_ ? eng_.device() : -1;
+  check_range_aligned("window scan", off, nelem, dtype);
+  check_range_inside("scan", off, nelem, dtype, 0, n);
   const int me = self_member();
-  auto drain = [&](const char* what) {
-    if (dev >= 0) hipw(hipStreamSynchronize(s), what);
-  };
-  if (dev >= 0) hipw(hipSetDevice(dev), "hipSetDevice");
-  drain("scan B1");
-  sync();  // B1: every member's input is complete
-  if (nelem > 0) {
-    // the slices of Window::allreduce's two-shot: interior bounds rounded down to a 16-B address
-    // of member 0's range, from the alignment member 0 published (the same on every rank)
-    auto bound = [&](int k) -> int64_t {
-      if (k <= 0) return 0;
-      if (k >= n) return nelem;
-      const int64_t b = nelem * k / n;
-      const int64_t a = ((int64_t(remote_[0].align) + off + b * es) & 15) / es;
-      return std::max<int64_t>(0, b - a);
-    };
-    const int64_t lo = bound(me), hi = bound(me + 1);
-    if (hi > lo) {
-      std::vector<uintptr_t> sl(static_cast<size_t>(n));
-      for (int m = 0; m < n; ++m)
-        sl[size_t(m)] = reinterpret_cast<uintptr_t>(remote_[size_t(m)].ptr) + uintptr_t(off + lo * es);
-      peer_scan(dev, s, op, dtype, exclusive, sl, sl, hi - lo);
-    }
-  }
-  drain("scan B2");
-  sync();  // B2: every prefix has landed at its owner and every read of my memory is finished
+  // the slices of Window::allreduce's two-shot
+  const int64_t lo = slice_bounds(me, n, nelem, off, es), hi = slice_bounds(me + 1, n, nelem, off, es);
+  const std::vector<uintptr_t> sl = member_ptrs(off + lo * es, 0, n);
+  epoch(s, "scan", [&](int dev) {
+    if (hi > lo) peer_scan(dev, s, op, dtype, exclusive, sl, sl, hi - lo);
+  });
   return true;
 }
 

@@ -17,6 +17,7 @@
 #include <array>
 #include <atomic>
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -182,7 +183,18 @@ class Window {
   // the span check of a plan against member m's window; the strided base address, 0 for an empty plan
   uintptr_t plan_base(int m, int64_t off, const CopyPlan& p, const char* outside) const;
   void copy_plan(int dir, int m, int64_t off, const CopyPlan& p, uintptr_t packed, hipStream_t s);
-  int self_member() const;  // my index among the members (throws when I am none)
+  int self_member(const char* who = "collective") const;  // my index among the members (throws when I am none)
+  // One epoch of a window collective: select the device, drain the stream, sync() (B1), launch(dev)
+  // with dev = -1 for a host window, drain, sync() (B2). Callers validate and throw before it;
+  // `launch` does not throw on validated arguments.
+  void epoch(hipStream_t s, const char* what, const std::function<void(int)>& launch);
+  // bound k of the n slices of a range, the same on every rank (two-shot all-reduce, scan)
+  int64_t slice_bounds(int k, int n, int64_t nelem, int64_t off, int64_t es) const;
+  // the range check of the reducing collectives, in two parts: aligned for dtype (invalid_argument),
+  // and inside the window of every member in [m0, m1) (out_of_range)
+  void check_range_aligned(const char* who, int64_t off, int64_t nelem, int dtype) const;
+  void check_range_inside(const char* who, int64_t off, int64_t nelem, int dtype, int m0, int m1) const;
+  std::vector<uintptr_t> member_ptrs(int64_t off, int m0, int m1) const;  // members' window bases + off
   void* ar_tmp_ = nullptr;  // one-shot in place: the private result, copied back after B2
   int64_t ar_tmp_bytes_ = 0;
 };

@@ -413,7 +413,7 @@ bool peer_dtype_is_pair(int dtype);
 void peer_reduce(int dev, hipStream_t s, int op, int dtype, const std::vector<uintptr_t>& srcs,
                  const std::vector<uintptr_t>& dsts, int64_t n);
 
-// ---- the kernels of the window collectives (peer_coll.hip) -----------------------------
+// ---- the kernels of the window collectives (peer_coll.hip; peer_fold: allreduce.hip) ---
 // One launch on `s` each, or the host twin for dev < 0. Element types, ops, widening, rounding
 // and combine are peer_reduce's: the same operands give the same bits. No pointer of a call
 // needs to share its offset within 16 B with another (element alignment is all that is asked).

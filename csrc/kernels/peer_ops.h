@@ -1,6 +1,8 @@
-// The element types and the combine of the predefined reductions, shared by the window
-// all-reduce (allreduce.hip) and the one-sided accumulate (type_acc.hip) so that both give the
-// same bits for the same operands: bf16 / fp16 widen to fp32 and round once, integers wrap,
+// The element types, the combine and the op switch (with_peer_op) of the predefined reductions,
+// shared by the window all-reduce and fold (allreduce.hip), the window scan (peer_coll.hip) and
+// the one-sided accumulate (type_acc.hip) so that all give the same bits for the same operands.
+// The streaming frame of the first three is peer_stream.h, next to this header.
+// bf16 / fp16 widen to fp32 and round once, integers wrap,
 // MAX / MIN propagate NaN, LAND / LOR / LXOR give 0 or 1 in the dtype, the bitwise ops are
 // integer-only (peer_reduce_supported). MAXLOC / MINLOC run on pair tags only: the element is a
 // whole (value, index) pair and the combine selects one operand, copied unchanged.
@@ -134,29 +136,38 @@ MPIT_HD void fold(typename Tag::A (&x)[NS][VE], int ns) {
   }
 }
 
-template <class Tag, int NS, int VE>
-MPIT_HD void fold_op(int op, typename Tag::A (&x)[NS][VE], int ns) {
-  if constexpr (Tag::kPair) {  // the two pair ops and nothing else (peer_reduce_supported)
-    if (op == kPrMaxloc) fold<Tag, kPrMaxloc, NS, VE>(x, ns);
-    else fold<Tag, kPrMinloc, NS, VE>(x, ns);
+// The one switch over the ten PeerOp: f(std::integral_constant<int, OP>{}) is called once for an
+// (op, Tag) that peer_reduce_supported allows. A pair tag has the two pair ops and nothing else,
+// a scalar tag the seven common ops, an integer tag the three bitwise ops as well. `op` is
+// wave-uniform: callers switch once per vector / item, outside their element loops.
+template <class Tag, class F>
+MPIT_HD void with_peer_op(int op, F&& f) {
+  if constexpr (Tag::kPair) {
+    if (op == kPrMaxloc) f(std::integral_constant<int, kPrMaxloc>{});
+    else f(std::integral_constant<int, kPrMinloc>{});
   } else {
     switch (op) {
-      case kPrSum: fold<Tag, kPrSum, NS, VE>(x, ns); break;
-      case kPrProd: fold<Tag, kPrProd, NS, VE>(x, ns); break;
-      case kPrMax: fold<Tag, kPrMax, NS, VE>(x, ns); break;
-      case kPrMin: fold<Tag, kPrMin, NS, VE>(x, ns); break;
-      case kPrLand: fold<Tag, kPrLand, NS, VE>(x, ns); break;
-      case kPrLor: fold<Tag, kPrLor, NS, VE>(x, ns); break;
-      case kPrLxor: fold<Tag, kPrLxor, NS, VE>(x, ns); break;
+      case kPrSum: f(std::integral_constant<int, kPrSum>{}); break;
+      case kPrProd: f(std::integral_constant<int, kPrProd>{}); break;
+      case kPrMax: f(std::integral_constant<int, kPrMax>{}); break;
+      case kPrMin: f(std::integral_constant<int, kPrMin>{}); break;
+      case kPrLand: f(std::integral_constant<int, kPrLand>{}); break;
+      case kPrLor: f(std::integral_constant<int, kPrLor>{}); break;
+      case kPrLxor: f(std::integral_constant<int, kPrLxor>{}); break;
       default:
         if constexpr (Tag::kInt) {
-          if (op == kPrBand) fold<Tag, kPrBand, NS, VE>(x, ns);
-          else if (op == kPrBor) fold<Tag, kPrBor, NS, VE>(x, ns);
-          else fold<Tag, kPrBxor, NS, VE>(x, ns);
+          if (op == kPrBand) f(std::integral_constant<int, kPrBand>{});
+          else if (op == kPrBor) f(std::integral_constant<int, kPrBor>{});
+          else f(std::integral_constant<int, kPrBxor>{});
         }
         break;
     }
   }
+}
+
+template <class Tag, int NS, int VE>
+MPIT_HD void fold_op(int op, typename Tag::A (&x)[NS][VE], int ns) {
+  with_peer_op<Tag>(op, [&](auto o) { fold<Tag, decltype(o)::value>(x, ns); });
 }
 
 // one call per element type of a PeerDtype code the caller has checked (peer_reduce_supported)

@@ -51,27 +51,7 @@ MPIT_HD void comb_all(const typename Tag::S (&t)[VE], const typename Tag::S (&o)
 template <class Tag, int VE>
 MPIT_HD void comb_op(int op, const typename Tag::S (&t)[VE], const typename Tag::S (&o)[VE],
                      typename Tag::S (&r)[VE]) {
-  if constexpr (Tag::kPair) {
-    if (op == kPrMaxloc) comb_all<Tag, kPrMaxloc, VE>(t, o, r);
-    else comb_all<Tag, kPrMinloc, VE>(t, o, r);
-    return;
-  }
-  switch (op) {
-    case kPrSum: comb_all<Tag, kPrSum, VE>(t, o, r); break;
-    case kPrProd: comb_all<Tag, kPrProd, VE>(t, o, r); break;
-    case kPrMax: comb_all<Tag, kPrMax, VE>(t, o, r); break;
-    case kPrMin: comb_all<Tag, kPrMin, VE>(t, o, r); break;
-    case kPrLand: comb_all<Tag, kPrLand, VE>(t, o, r); break;
-    case kPrLor: comb_all<Tag, kPrLor, VE>(t, o, r); break;
-    case kPrLxor: comb_all<Tag, kPrLxor, VE>(t, o, r); break;
-    default:
-      if constexpr (Tag::kInt && !Tag::kPair) {
-        if (op == kPrBand) comb_all<Tag, kPrBand, VE>(t, o, r);
-        else if (op == kPrBor) comb_all<Tag, kPrBor, VE>(t, o, r);
-        else comb_all<Tag, kPrBxor, VE>(t, o, r);
-      }
-      break;
-  }
+  with_peer_op<Tag>(op, [&](auto c) { comb_all<Tag, decltype(c)::value, VE>(t, o, r); });
 }
 
 template <class Tag, typename V, typename IT, int MODE>

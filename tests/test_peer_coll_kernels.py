@@ -1,6 +1,7 @@
 """The kernels of the window collectives (csrc/kernels/peer_coll.hip) through their raw bindings,
-one process: peer_gather, peer_fold and peer_scan, the host twins (dev = -1) on the CPU tier and
-the gfx950 kernels on the GPU tier. Every comparison is bitwise: against the source bytes
+one process: peer_gather, peer_fold and peer_scan, and peer_reduce's vector body (every pointer
+at one offset within 16 bytes), the host twins (dev = -1) on the CPU tier and the gfx950 kernels
+on the GPU tier. Every comparison is bitwise: against the source bytes
 (peer_gather), against the left fold in the order given computed with torch on the CPU (16-bit
 floats folded in fp32 and cast once) and against peer_reduce on the same operands (peer_fold,
 peer_scan). Guards around every destination and the sources themselves must stay as they were."""
@@ -266,3 +267,79 @@ def test_peer_scan_every_other_pair_once(device):
     for oname, dname in OTHER_PAIRS:
         scan_case(device, oname, dname, 1031, 3, False, True, 0)
         scan_case(device, oname, dname, 1031, 3, True, False, 0)
+
+
+# ------------------------------------------------------------------ peer_reduce, vector body
+VEC_PAIRS = PAIRS + [("PROD", "f16")]  # (the generator's zeros and negative values make exact -0 products)
+VOFFS = [0, 1, 3]  # elements past a 16-byte boundary, the same for every pointer of a call
+
+
+@functools.lru_cache(maxsize=None)
+def shared_sources(dname, off):
+    """The eight sources again (the operands of prefixes()), each moved to `off` elements past a
+    16-byte boundary of a host buffer of its own, other values around them."""
+    out = []
+    for k, b in enumerate(sources(dname)):
+        t = gen(DT[dname], 90 + k, off + NMAX + G)
+        t[off: off + NMAX] = b[SRC_OFFS[k]: SRC_OFFS[k] + NMAX]
+        out.append(t)
+    return tuple(out)
+
+
+@functools.lru_cache(maxsize=None)
+def shared_on_device(dname, off, device):
+    return tuple(b.clone().to(device) for b in shared_sources(dname, off))
+
+
+@functools.lru_cache(maxsize=None)
+def twin_reduce(oname, dname, ns):
+    """peer_reduce's host twin (dev = -1) over all NMAX elements of the first ns sources; computed once."""
+    dt = DT[dname]
+    out = torch.zeros(NMAX, dtype=dt)
+    native().peer_reduce(-1, 0, C._PR_OP_CODE[OPS[oname]], C._PR_DTYPES[dt],
+                         [b.data_ptr() for b in shared_sources(dname, 0)[:ns]], [out.data_ptr()], NMAX)
+    return out
+
+
+def reduce_case(device, oname, dname, cnt, off, ns, nd, inplace):
+    dt = DT[dname]
+    code, dcode = C._PR_OP_CODE[OPS[oname]], C._PR_DTYPES[dt]
+    host = shared_sources(dname, off)
+    es = host[0].element_size()
+    if inplace:  # dsts = srcs[:nd], on copies; what surrounds the range is the guard
+        work = [b.clone() for b in shared_on_device(dname, off, device)[:ns]]
+        outs, guards, at = work[:nd], host[:nd], off
+        sp = [w.data_ptr() + off * es for w in work]
+    else:
+        work = shared_on_device(dname, off, device)[:ns]
+        guard = gen(dt, 79, G + 3 + NMAX + G)[: G + off + cnt + G]
+        outs, guards, at = [guard.clone().to(device) for _ in range(nd)], [guard] * nd, G + off
+        sp = [w.data_ptr() + off * es for w in work]
+    dp = [o.data_ptr() + at * es for o in outs]
+    assert all(p % 16 == off * es % 16 for p in sp + dp)  # one offset within 16 bytes: the vector body
+    dev, stream = dev_of(device)
+    native().peer_reduce(dev, stream, code, dcode, sp, dp, cnt)
+    done(device)
+    tag = (oname, dname, cnt, off, ns, nd, inplace)
+    for j in range(nd):
+        want = guards[j].clone()
+        want[at: at + cnt] = prefixes(oname, dname)[ns - 1][:cnt]
+        assert same(outs[j], want), (tag, j)  # the CPU left fold, and the guards
+        assert same(outs[j][at: at + cnt], twin_reduce(oname, dname, ns)[:cnt]), (tag, j, "host twin differs")
+    for k in range(nd if inplace else 0, ns):
+        assert same(work[k], host[k]), (tag, k, "source modified")
+
+
+@pytest.mark.parametrize("device", DEVICES)
+@pytest.mark.parametrize("oname,dname", VEC_PAIRS)
+def test_peer_reduce_vector_body(device, oname, dname):
+    """Every source and destination at one offset {0, 1, 3} elements past a 16-byte boundary, so
+    that peer_reduce runs its vector body between a scalar head and tail: counts x ns {1, 2, 3, 5, 8}
+    x nd {1, 3}, and in place (dsts = srcs[:3] of 5). Bitwise against the CPU left fold (wide
+    accumulate, one rounding), guards included, and against the host twin."""
+    for cnt in COUNTS:
+        for off in VOFFS:
+            for ns in NS:
+                for nd in (1, 3):
+                    reduce_case(device, oname, dname, cnt, off, ns, nd, False)
+            reduce_case(device, oname, dname, cnt, off, 5, 3, True)
